@@ -12,11 +12,17 @@ rank-1 pass over the n*n f64 matrix, driven from a device-resident queue of synt
 N > 1: Q is row-block partitioned over the ranks (same n: strong scaling); every update does one
 in-place RCCL all-gather of the n-vector Q*g between the two passes.
 
-Besides the contract fields the line carries
-  roofline     : HBM roofline of the dominant kernel (k_rank1, 16*n^2 algorithmic bytes per launch),
-                 its duration measured with HIP events on the launch stream; per-kernel and
-                 whole-update (24*n^2 B) figures alongside.
+A plain run sets up, warms up, times the --steps steps and prints the line (contract fields, the
+configuration and the whole-update byte model of the timed region).  With --full the line also carries
+  roofline     : HBM roofline of the dominant kernel, its duration measured with HIP events on the
+                 launch stream in extra profiled steps; per-kernel figures alongside.
   cpu_baseline : the CPU oracle (reference loop order, 1 thread) timed on this box, rank 0, N = 1.
+and the other schedules / depths, the host-call path, the live loop and BASELINE's other configurations.
+
+--dump-outputs DIR writes what the timed path computed (after its last step) as DIR/<name>.npy, float64:
+the per-cut results of the timed steps, the centre, kappa and a fixed, seeded sample of the matrix.
+The inputs are seeded: the same arguments give the same inputs on every run.  The cut offsets follow the
+ellipsoid's predicted size (track_tsq), so a run of any --steps keeps every cut valid.
 """
 from __future__ import annotations
 
@@ -77,6 +83,123 @@ def log(*a):
     print(*a, file=sys.stderr, flush=True)
 
 
+def track_tsq(n: int, kinds, b0, b1):
+    """The synthetic cut offsets as fractions of the ellipsoid's current size: (b0, b1) of cut k scaled by a predicted
+    sqrt(tsq_k), so that a run of any length keeps cutting the way its first cuts do.  Absolute offsets do not: tsq shrinks
+    with every update (kappa by about 1 - b0^2 per parallel-bias cut, whatever n), and after about two thousand cuts
+    b1^2 >= tsq (the parallel cut degenerates to a single one) and then b0^2 > tsq (NoSoln).  delta and sigma of EllCalc
+    depend on the offsets only through b / sqrt(tsq), so the prediction is a running product taken from the unscaled
+    offsets at tsq = 1 (Q0 = I, kappa0 = 1, unit gradients): kappa *= delta exactly, and g'Qg of the next random unit
+    gradient is taken as trace(Q) / n, which shrinks by sigma / n per update (Q -= sigma Qg(Qg)' / g'Qg, |Qg|^2 ~ (g'Qg)^2).
+    That mean is what drifts: over 2500 cuts the real tsq stays within 0.97-1.02 of the prediction at n = 2048 and within
+    0.79-1.04 at n = 512 (parallel cuts) -- inside the factor 4 that the largest fraction (b1 < 0.5 sqrt(tsq)) leaves.
+    Deterministic: the same arguments give the same cuts."""
+    b0 = np.asarray(b0, dtype=np.float64)
+    b1 = np.asarray(b1, dtype=np.float64)
+    nf = float(n)
+    cst1 = nf * nf / (nf * nf - 1.0)
+    par = ~np.isnan(b1)
+    c1 = np.where(par, b1, 0.0)
+    # parallel central cut (kind 1 with b1), src/ell_calc.rs:383-394
+    a1sq = c1 * c1
+    half_val = nf / 2.0 * a1sq
+    root = half_val + np.sqrt(1.0 - a1sq + half_val * half_val)
+    sig_pc, del_pc = 2.0 / (root + 1.0), root / (root - 1.0 / nf)
+    # parallel bias cut (kind 0 with b1), src/ell_calc.rs:218-240
+    zeta0, zeta1 = 1.0 - b0 * b0, 1.0 - a1sq
+    temp = nf / 2.0 * (a1sq - b0 * b0)
+    xi = np.sqrt(zeta0 * zeta1 + temp * temp)
+    sig_pb = 2.0 * (1.0 + nf * b0 * c1) / (1.0 + b0 * c1 + nf / 2.0 * (b0 + c1) ** 2 + xi)
+    del_pb = cst1 * ((zeta0 + zeta1) / 2.0 + xi / nf)
+    # bias cut (kind 0 without b1) and central cut, src/ell_calc.rs:453-459, 605-611
+    sig_b, del_b = 2.0 * (1.0 + nf * b0) / ((nf + 1.0) * (1.0 + b0)), cst1 * (1.0 - b0 * b0)
+    sig_c, del_c = 2.0 / (nf + 1.0), cst1
+    central = np.asarray(kinds) == 1
+    sigma = np.where(par, np.where(central, sig_pc, sig_pb), np.where(central, sig_c, sig_b))
+    delta = np.where(par, np.where(central, del_pc, del_pb), np.where(central, del_c, del_b))
+    log_tsq = np.concatenate(([0.0], np.cumsum(np.log(delta) + np.log1p(-sigma / nf))[:-1]))
+    tau = np.exp(0.5 * log_tsq)
+    return b0 * tau, b1 * tau
+
+
+def unit_gaussians(seeds, n: int) -> np.ndarray:
+    """synth.unit_gaussian(seed, n) for every seed, as the rows of one block: the same splitmix64 counter stream, Box-Muller
+    and normalisation, bit for bit (every elementwise step on contiguous data, the norm by np.dot per row, as synth does)."""
+    m = (n + 1) // 2
+    with np.errstate(over="ignore"):
+        z = np.asarray(seeds, dtype=np.uint64)[:, None] + np.arange(1, 2 * m + 1, dtype=np.uint64) * np.uint64(0x9E3779B97F4A7C15)
+        z ^= z >> np.uint64(30)
+        z *= np.uint64(0xBF58476D1CE4E5B9)
+        z ^= z >> np.uint64(27)
+        z *= np.uint64(0x94D049BB133111EB)
+        z ^= z >> np.uint64(31)
+    u = ((z >> np.uint64(11)).astype(np.float64) + 0.5) * (1.0 / 9007199254740992.0)
+    r = np.sqrt(-2.0 * np.log(np.ascontiguousarray(u[:, :m])))
+    t = 2.0 * np.pi * np.ascontiguousarray(u[:, m:])
+    g = np.empty((len(u), 2 * m), dtype=np.float64)
+    g[:, 0::2] = r * np.cos(t)
+    g[:, 1::2] = r * np.sin(t)
+    g = g[:, :n]
+    return g / np.sqrt(np.array([np.dot(row, row) for row in g]))[:, None]
+
+
+def cut_stream(synth, cutgen: str, n: int, count: int):
+    """`count` cuts of the workload's generator (synth.parallel_cuts / synth.deep_cuts, the same values) with offsets that
+    follow the ellipsoid's size (track_tsq).  synth builds one gradient per Python iteration, ~0.3 ms at n = 16384, which
+    made a long run's set-up grow far faster than its steps; here blocks of gradients are built at once on the CPUs this
+    process may use, so the set-up stays a small fraction of the timed steps at any --steps."""
+    from concurrent.futures import ThreadPoolExecutor
+    grads = np.empty((count, n), dtype=np.float64)
+    block = 16
+
+    def fill(i0: int) -> None:
+        i1 = min(i0 + block, count)
+        grads[i0:i1] = unit_gaussians(synth.SEED0 + np.arange(i0, i1, dtype=np.int64), n)
+
+    cpus = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+    with ThreadPoolExecutor(max(1, min(cpus, 16))) as pool:   # numpy releases the GIL in these loops
+        list(pool.map(fill, range(0, count, block)))
+    if cutgen == "parallel":   # synth.parallel_cuts: even cuts parallel-central, odd ones parallel-bias
+        u = synth.uniform01(synth.SEED0 ^ 0xBE7A, 2 * count)
+        even = np.arange(count) % 2 == 0
+        kinds = np.where(even, 1, 0).astype(np.int32)
+        b0 = np.where(even, 0.0, 0.05 * u[0::2])
+        b1 = np.where(even, 0.05 + 0.45 * u[0::2], b0 + 0.05 + 0.40 * u[1::2])
+    else:                      # synth.deep_cuts
+        kinds = np.zeros(count, dtype=np.int32)
+        b0 = 0.1 * synth.uniform01(synth.SEED0 ^ 0xBE7A, count)
+        b0[220:] *= 0.2
+        b1 = np.full(count, np.nan)
+    b0, b1 = track_tsq(n, kinds, b0, b1)
+    return kinds, grads, b0, b1
+
+
+DUMP_LIMIT_BYTES = 64 << 20   # --dump-outputs: at most this much in all
+DUMP_SAMPLE = 1 << 20         # entries of a matrix (or a stack of them) kept when it is larger than that
+
+
+def dump_sample(a, count: int = DUMP_SAMPLE, seed: int = 0x5EED) -> np.ndarray:
+    """A fixed, seeded sample of `count` entries of `a` (flattened, sorted positions; all of it when it is not larger): the
+    positions depend on the size only, so two runs of the same arguments sample the same entries."""
+    flat = np.asarray(a).reshape(-1)
+    if flat.size <= count:
+        return flat.astype(np.float64)
+    idx = np.sort(np.random.default_rng(seed).integers(0, flat.size, count, dtype=np.int64))
+    return flat[idx].astype(np.float64)
+
+
+def write_outputs(path: str, arrays: dict) -> None:
+    """--dump-outputs: one DIR/<name>.npy per array, float64."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(np.atleast_1d(np.asarray(v, dtype=np.float64))) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES} byte limit")
+    for k, v in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), v)
+    log(f"[dump] {len(arrays)} arrays ({total / 2**20:.1f} MiB) in {path}: {', '.join(sorted(arrays))}")
+
+
 # SURVEY 8 row f3: many independent small ellipsoids (BASELINE config 1 is n = 16) in one launch.
 BATCH_WORKLOADS = {"batch-n16": (16, 65536, 8), "batch-n32": (32, 32768, 8), "batch-n64": (64, 8192, 8),
                    "batch-n128": (128, 2048, 8)}
@@ -119,18 +242,23 @@ def batch_bench(args, real_stdout) -> None:
     batch.synchronize()
     elapsed = time.perf_counter() - t0
     assert bool((status == 0).all().item()), "a cut did not succeed"
-    # kernel duration with HIP events on the launch stream (torch.cuda.Event only sees torch's stream)
-    stream = torch.cuda.ExternalStream(batch._lib.ellhip_batch_stream(batch._h))
-    evs = []
-    for _ in range(min(S, 20)):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record(stream)
-        launch()
-        b.record(stream)
-        evs.append((a, b))
-    batch.synchronize()
-    kern_ms = float(np.mean([a.elapsed_time(b) for a, b in evs]))
+    if args.dump_outputs:
+        write_outputs(args.dump_outputs, {"status": status.cpu().numpy(), "xc": batch.xc(), "kappa": batch.kappa,
+                                          "tsq": batch.tsq(), "q_sample": dump_sample(batch.mq)})
     alg = B * (16.0 * n * n + K * (n * 8.0 + 24.0) + 16.0 * n + 32.0)
+    # kernel duration with HIP events on the launch stream (torch.cuda.Event only sees torch's stream): --full only
+    kern_ms = elapsed / S * 1e3
+    if args.full:
+        stream = torch.cuda.ExternalStream(batch._lib.ellhip_batch_stream(batch._h))
+        evs = []
+        for _ in range(min(S, 20)):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record(stream)
+            launch()
+            b.record(stream)
+            evs.append((a, b))
+        batch.synchronize()
+        kern_ms = float(np.mean([a.elapsed_time(b) for a, b in evs]))
     gbps = alg / (kern_ms * 1e-3) / 1e9
     out = {
         "metric": "ellipsoid updates/sec, %d independent ellipsoids of n=%d (batched engine)" % (B, n),
@@ -139,7 +267,8 @@ def batch_bench(args, real_stdout) -> None:
         "dtype": "f64", "data": "synthetic",
         "config": {"workload": args.workload, "n": n, "ellipsoids": B, "cuts_per_launch": K, "space": "ell",
                    "cuts": "central, random unit gradients", "q_bytes_total": 8.0 * n * n * B},
-        "roofline": {"bound": "hbm", "peak": HBM_PEAK_GBS, "unit": "GB/s", "kernel": "k_batch_update",
+        "roofline": {"bound": "hbm", "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                     "kernel": "k_batch_update" if args.full else "whole launch (timed region, wall clock)",
                      "achieved": gbps, "frac": gbps / HBM_PEAK_GBS, "traffic": None, "alg_bytes_per_launch": alg,
                      "avg_launch_ms": kern_ms,
                      "byte_model": "per ellipsoid and launch: Q in + out 16*n^2, K gradients K*n*8, cut values and "
@@ -153,7 +282,7 @@ def batch_bench(args, real_stdout) -> None:
             out["roofline"]["traffic_source"] = pmc.get("source")
     except OSError:
         pass
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         from oracle import oracle as O
         log("[batch] timing the CPU oracle (bounded sample) ...")
         Bs = min(B, 2048)
@@ -201,24 +330,30 @@ def lmi_bench(args, real_stdout) -> None:
     dev = pkg.LMIOracle(F, B)
     log(f"[lmi] {n} matrices {m} x {m} ({n * m * m * 8 / 2**30:.2f} GiB) uploaded in {time.perf_counter() - t0:.1f}s")
     assert dev.assess_feas(x_feas) is None
-    scale = 0.25  # walk out along x_dir until F(x) stops being positive definite
-    while dev.assess_feas(scale * x_dir) is None:
-        scale *= 1.5
-        assert scale < 1e6
-    x_cut = scale * x_dir
-    cut = dev.assess_feas(x_cut)
-    p_cut = dev.pos[1]
 
     def timed(x, count):
         for _ in range(W):
             dev.assess_feas(x)
         t1 = time.perf_counter()
         for _ in range(count):
-            dev.assess_feas(x)
-        return (time.perf_counter() - t1) / count
+            r = dev.assess_feas(x)
+        return (time.perf_counter() - t1) / count, r
 
-    t_feas = timed(x_feas, S)
-    t_cut = timed(x_cut, S)
+    t_feas, r_feas = timed(x_feas, S)
+    if args.dump_outputs:   # a feasible point: no cut; the caller's result is that, and the factor the call left behind
+        write_outputs(args.dump_outputs, {"feasible": float(r_feas is None), "ldlt_storage_sample": dump_sample(dev.storage)})
+    cut_case = None
+    if args.full:   # the infeasible point (the factorisation stops at the failing pivot), timed the same way
+        scale = 0.25  # walk out along x_dir until F(x) stops being positive definite
+        while dev.assess_feas(scale * x_dir) is None:
+            scale *= 1.5
+            assert scale < 1e6
+        x_cut = scale * x_dir
+        cut = dev.assess_feas(x_cut)
+        p_cut = dev.pos[1]
+        t_cut, _ = timed(x_cut, S)
+        cut_case = {"ms_per_call": t_cut * 1e3, "failing_row": p_cut,
+                    "note": "factorisation stops at the failing pivot; witness + n quadratic forms follow"}
     form_bytes = n * m * (m + 1) / 2 * 8.0
     flops = m ** 3 / 3.0 * 2.0
     out = {
@@ -226,8 +361,7 @@ def lmi_bench(args, real_stdout) -> None:
         "value": 1.0 / t_feas, "unit": "calls/s", "n_gpus": 1, "steps": S, "warmup": W, "ms_per_step": t_feas * 1e3,
         "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
         "config": {"workload": args.workload, "n": n, "m": m, "pencil_bytes": 8.0 * n * m * m,
-                   "cut_case": {"ms_per_call": t_cut * 1e3, "failing_row": p_cut,
-                                "note": "factorisation stops at the failing pivot; witness + n quadratic forms follow"}},
+                   **({"cut_case": cut_case} if cut_case else {})},
         "roofline": {"bound": "hbm", "peak": HBM_PEAK_GBS, "unit": "GB/s", "kernel": "whole call", "traffic": None,
                      "achieved": form_bytes / t_feas / 1e9, "frac": form_bytes / t_feas / 1e9 / HBM_PEAK_GBS,
                      "byte_model": "lower triangle of the n matrices read once to form F(x): n*m*(m+1)/2*8 B; the call is "
@@ -235,7 +369,7 @@ def lmi_bench(args, real_stdout) -> None:
                      "factor_gflops": flops / t_feas / 1e9,
                      "whole_update": {"frac": form_bytes / t_feas / 1e9 / HBM_PEAK_GBS}},
     }
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         from oracle import oracle as O
         log("[lmi] timing the CPU oracle (bounded sample) ...")
         cpu = O.OracleLMI(F, B)
@@ -284,16 +418,19 @@ def lowpass_bench(args, real_stdout) -> None:
     oracle.rows_visited(reset=True)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    _, nit, gamma = oracle.cutting_plane_optim(space, gamma, K, 0.0)
+    x_best, nit, gamma = oracle.cutting_plane_optim(space, gamma, K, 0.0)
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     if nit != K:
         raise SystemExit(f"the run reached its natural end after {W + nit} iterations (no further improvement of gamma "
                          f"is possible: NoSoln): use fewer --steps for {args.workload}")
     rows_timed = oracle.rows_visited(reset=True)
+    if args.dump_outputs:
+        write_outputs(args.dump_outputs, {"x_best": np.full(n, np.nan) if x_best is None else x_best, "gamma": gamma,
+                                          "xc": space.xc(), "kappa": space.kappa, "q_sample": dump_sample(space.mq)})
 
     per_kernel, rows_prof = {}, 0
-    if P > 0:
+    if args.full and P > 0:
         space.profile_enable(True)
         _, nit, gamma = oracle.cutting_plane_optim(space, gamma, P, 0.0)
         assert nit == P
@@ -345,7 +482,7 @@ def lowpass_bench(args, real_stdout) -> None:
                    "gamma_after": gamma},
         "roofline": roofline,
     }
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         from oracle import oracle as O
         log("[lowpass] timing the CPU oracle loop (bounded sample) ...")
         t0 = time.perf_counter()
@@ -487,6 +624,9 @@ def ell_bytes_per_update(n2w: float, sched: str, dep: int, steps: int, symv_mode
                        f"{steps} updates (deferred shrink, depth {dep})")
 
 
+RESIDENT_MAX_N = 4224   # include/ellhip.h, ELLHIP_OPT_RESIDENT: the largest n whose lower triangle fits the register files of 256 CUs
+
+
 # the BASELINE.json configurations besides the headline one, with the brief (steps, warmup, profile steps) they are run
 # at inside the default invocation so that the driver's one line carries all of them
 BRIEF_CONFIGS = [("n4096-deep", 200, 20, 40), ("n32768-deep", 96, 16, 16), ("n16384-ellstable", 48, 8, 16)]
@@ -548,7 +688,7 @@ def brief_config(pkg, synth, torch, workload: str, K: int, W: int, P: int, devic
     figures `other_configs` carries."""
     n, variant, cutgen, desc = WORKLOADS[workload]
     t_gen = time.perf_counter()
-    kinds, grads, b0, b1 = (synth.parallel_cuts if cutgen == "parallel" else synth.deep_cuts)(n, W + K + P)
+    kinds, grads, b0, b1 = cut_stream(synth, cutgen, n, W + K + P)
     if variant == "ell":
         space = pkg.Ell.new_with_scalar(1.0, np.zeros(n), device=device)
         depth = space.defer_depth
@@ -655,6 +795,13 @@ def main() -> None:
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--workload", default=os.environ.get("ELLHIP_BENCH_WORKLOAD", "n16384-parallel"),
                     choices=sorted(WORKLOADS) + sorted(LOWPASS_WORKLOADS) + sorted(BATCH_WORKLOADS) + sorted(LMI_WORKLOADS))
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps, measure everything else the line has carried: per-kernel HIP events, the other "
+                         "schedules / depths, the host-call path, the live loop, the CPU baseline and BASELINE's other "
+                         "configurations (the options below that size those legs apply with --full only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they computed as DIR/<name>.npy (float64, at most 64 MiB: per-cut "
+                         "status and tsq of the timed steps, xc, kappa, the diagonal and a fixed, seeded sample of Q)")
     ap.add_argument("--profile-steps", type=int, default=40, help="extra steps with per-kernel HIP events")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-budget", type=float, default=20.0)
@@ -677,8 +824,8 @@ def main() -> None:
     ap.add_argument("--force-sharded", action="store_true",
                     help="run the row-partitioned (multi-GPU) code path even with one rank (rehearsal)")
     ap.add_argument("--other-configs", choices=["auto", "on", "off"], default="auto",
-                    help="after the headline run, time the other BASELINE.json configurations briefly in the same process and "
-                         "report them as `other_configs` (auto: with the default workload on one GPU)")
+                    help="with --full: after the headline run, time the other BASELINE.json configurations briefly in the same "
+                         "process and report them as `other_configs` (auto: with the default workload on one GPU)")
     ap.add_argument("--opt", action="append", default=[], metavar="KEY=VALUE",
                     help="ellhip_set_default_option before any handle is created, e.g. --opt APPLY_KERNEL=2 (A/B runs; keys: "
                          "the ELLHIP_OPT_* names of include/ellhip.h without the prefix)")
@@ -691,6 +838,8 @@ def main() -> None:
     if args.all_configs:
         if args.gpus != 1 or int(os.environ.get("WORLD_SIZE", "1")) != 1:
             raise SystemExit("--all-configs is a one-GPU run")
+        if args.dump_outputs:
+            raise SystemExit("--dump-outputs writes the outputs of one workload: run it without --all-configs")
         import subprocess
         rc = 0
         for wl in ALL_CONFIGS:
@@ -699,6 +848,8 @@ def main() -> None:
                    "--host-path-steps", str(args.host_path_steps), "--cpu-budget", str(args.cpu_budget)]
             if args.no_cpu_baseline:
                 cmd.append("--no-cpu-baseline")
+            if args.full:
+                cmd.append("--full")
             log(f"[all-configs] {wl}")
             out = subprocess.run(cmd, stdout=subprocess.PIPE, text=True)   # the child parks its own stdout the same way
             rc = rc or out.returncode
@@ -745,7 +896,11 @@ def main() -> None:
         key, _, val = kv.partition("=")
         pkg.capi.set_default_option(getattr(pkg.capi, "OPT_" + key.strip().upper()), int(val))
     n, variant, cutgen, desc = WORKLOADS[args.workload]
-    K, W, P = args.steps, args.warmup, args.profile_steps
+    if args.dump_outputs and sharded:
+        raise SystemExit("--dump-outputs: unsharded runs only (one GPU, without --force-sharded)")
+    # a plain run times the K steps and nothing else: every other region below runs with --full only
+    full = args.full
+    K, W, P = args.steps, args.warmup, (args.profile_steps if full else 0)
     # EllStable does not shard (its triangular solves are sequential along the partitioned dimension): with N > 1
     # every rank runs an independent replica on its own GPU, no collective in the data path ("replicas only",
     # DESIGN.md section 7); the process group is used for the fences and the max-over-ranks clock only.
@@ -753,7 +908,7 @@ def main() -> None:
     replicas = sharded and variant != "ell"
     if replicas:
         sharded = False
-    H = args.host_path_steps if not multi else 0
+    H = args.host_path_steps if (full and not multi) else 0
     fused = args.schedule == "pipelined" and variant == "ell"
     depth = args.defer if variant == "ell" else 1
     opt = pkg.capi.default_option
@@ -767,7 +922,7 @@ def main() -> None:
             # per group of up to 32 queued cuts): the per-cut latency that made small trapezoids a loss is gone
             sym = (n % 64 == 0 and n // 64 >= world and os.environ.get("ELLHIP_SHARD_SYMMETRIC", "1") != "0")
             depth = 24 if (lower_ok and sym) else 8
-    C2 = args.compare_steps if variant == "ell" else 0
+    C2 = args.compare_steps if (full and variant == "ell") else 0
     # N > 1, depth 8: symmetric row shards (equal lower-trapezoid areas, partial symmetric GEMVs added by one
     # all-reduce, lower-trapezoid apply passes): 5*n^2/P bytes per GPU and update.  That schedule only, so the
     # other schedules are not timed alongside.
@@ -781,7 +936,7 @@ def main() -> None:
         C2 = 0
     # symmetric shards: a second timed region on the schedule BASELINE config 4 names -- one all-reduce of Q g per ITERATION
     # (the headline region takes the queue in groups: one all-reduce per group of up to 32 queued cuts, replay only)
-    C3 = 48 if shard_sym else 0
+    C3 = 48 if (full and shard_sym) else 0
     # alternatives measured after the main run, on the same handle: (schedule, depth)
     alts = []
     if C2 > 0:
@@ -798,13 +953,13 @@ def main() -> None:
     P_iso = P if (variant == "ell" and not sharded and args.schedule == "pipelined" and n % 64 == 0 and n >= symv_min_n and lower_ok) else 0
     # a second, longer region of the SAME schedule when the contract's K is short (the driver runs --steps 20: a 1.25 ms
     # single shot whose one apply pass is a third of it): `config.steady_state_updates_per_s`, never `value`
-    S2 = 192 if (variant == "ell" and not sharded and K < 192) else 0
+    S2 = 192 if (full and variant == "ell" and not sharded and K < 192) else 0
     total = W + K + P + P_iso + 2 * C2 * len(alts) + C3 + S2 + H
     if sharded and n % world and not shard_sym:
         raise SystemExit(f"n={n} is not divisible by {world} ranks")
 
     t_gen = time.perf_counter()
-    kinds, grads, b0, b1 = (synth.parallel_cuts if cutgen == "parallel" else synth.deep_cuts)(n, total)
+    kinds, grads, b0, b1 = cut_stream(synth, cutgen, n, total)
     log(f"[rank {rank}] generated {total} cuts for {args.workload} in {time.perf_counter() - t_gen:.1f}s")
 
     # ---- build the search space (Q0 = I, xc0 = 0, kappa0 = 1)
@@ -896,6 +1051,14 @@ def main() -> None:
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+
+    # ---- what the timed steps computed, read back before anything else runs on the handle
+    if args.dump_outputs:
+        st_d, ts_d = space.queue_results()
+        mq = space.mq
+        write_outputs(args.dump_outputs, {"status": st_d[W:W + K], "tsq": ts_d[W:W + K], "xc": space.xc(), "kappa": space.kappa,
+                                          "q_diag": np.diagonal(mq).copy(), "q_sample": dump_sample(mq)})
+        del mq
 
     # ---- per-kernel durations with HIP events on the launch stream (outside the timed region)
     prof = None
@@ -1021,7 +1184,7 @@ def main() -> None:
     # ---- the live loop: xc() -> host oracle -> update, through the C++ drivers over the C ABI (N = 1 only)
     live_loop = None
     if H > 0 and args.live_loop_steps > 0:
-        live_loop = run_live_loop(pkg, synth, synth.parallel_cuts if cutgen == "parallel" else synth.deep_cuts, n, kinds, grads,
+        live_loop = run_live_loop(pkg, synth, lambda n_, k_: cut_stream(synth, cutgen, n_, k_), n, kinds, grads,
                                   b0, b1, variant, args.live_loop_steps)
 
     if rank != 0:
@@ -1085,7 +1248,12 @@ def main() -> None:
     per_kernel = kernel_table(prof)
     # bytes one update moves under the schedule that was timed (each schedule has its OWN byte model;
     # nothing is credited against the 24*n^2 two-pass model)
-    resident_run = variant == "ell" and bool(prof) and prof.get("resident", (0.0, 0))[1] > 0
+    if prof:
+        resident_run = variant == "ell" and prof.get("resident", (0.0, 0))[1] > 0
+    else:   # (no profile in a plain run) the rule of include/ellhip.h, ELLHIP_OPT_RESIDENT: an unsharded Ell queue run of >= 4
+            # cuts parks the lower triangle on-chip while n <= RESIDENT_MAX_N, unless the handle has fallen back (it reads 0)
+        resident_run = (variant == "ell" and not sharded and K >= 4 and n <= RESIDENT_MAX_N
+                        and space.get_option(pkg.capi.OPT_RESIDENT) != 0)
     if variant != "ell" and space.get_option(pkg.capi.OPT_STABLE_MIRRORED):
         bytes_update, model = 8.0 * n * n, ("8*n^2 B per update (EllStable, mirrored layout: the forward solve reads the factor's upper "
                                             "triangle, the backward solve its mirrored copy, 4 + 4; nothing is rewritten -- the factor "
@@ -1249,10 +1417,10 @@ def main() -> None:
                                       f"`value` is the contract's {K}-step region, {ms_per_step * K:.2f} ms long, whose closing apply pass "
                                       "is a large part of it")
     out["config"].update(reach)
-    if world == 1 and not args.no_cpu_baseline:
+    if full and world == 1 and not args.no_cpu_baseline:
         log("[rank 0] timing the CPU oracle (bounded sample) ...")
         out["cpu_baseline"] = cpu_baseline(n, variant, kinds, grads, b0, b1, args.cpu_budget)
-    want_others = args.other_configs == "on" or (args.other_configs == "auto" and args.workload == "n16384-parallel")
+    want_others = full and (args.other_configs == "on" or (args.other_configs == "auto" and args.workload == "n16384-parallel"))
     if world == 1 and not args.force_sharded and want_others:
         # BASELINE.json's other configurations (2, 4 in its one-GPU form, 5), briefly, on the same process and GPU
         del space, grads

@@ -4,6 +4,8 @@ carries.  Reference quantities: one update = src/ell.rs:97-137 (GEMV 8 n^2 + ran
 import importlib.util
 import os
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 spec = importlib.util.spec_from_file_location("bench_model", os.path.join(ROOT, "bench.py"))
 bench = importlib.util.module_from_spec(spec)
@@ -60,3 +62,68 @@ def test_product_pass_roof_crosses_the_ridge_at_twenty_gradients():
     assert abs(r32["hbm_frac"] - 0.3016) < 1e-3      # the same launch against HBM: 4 n^2 bytes in 0.445 ms
     # a row shard: a quarter of the elements, a quarter of the flop and of the bytes, the same intensity
     assert bench.product_pass_roof(n2 / 4, 32, 0.2)["flop_per_byte"] == 16.0
+
+
+def test_dump_sample_is_seeded_and_complete_when_small():
+    import numpy as np
+    a = np.arange(3000 * 1000, dtype=np.float64).reshape(3000, 1000)
+    s1, s2 = bench.dump_sample(a, 4096), bench.dump_sample(a.copy(), 4096)
+    assert s1.dtype == np.float64 and s1.shape == (4096,) and np.array_equal(s1, s2)   # positions depend on the size only
+    assert np.all(np.diff(s1) >= 0) and np.all(np.isin(s1, a))
+    small = np.arange(12, dtype=np.int32).reshape(3, 4)
+    assert np.array_equal(bench.dump_sample(small, 4096), np.arange(12.0))
+
+
+def test_write_outputs_float64_and_limit(tmp_path):
+    import numpy as np
+    import pytest
+    bench.write_outputs(str(tmp_path / "d"), {"status": np.zeros(3, dtype=np.int32), "kappa": 2.5, "xc": np.ones(4)})
+    got = {f: np.load(tmp_path / "d" / f) for f in os.listdir(tmp_path / "d")}
+    assert set(got) == {"status.npy", "kappa.npy", "xc.npy"} and all(v.dtype == np.float64 for v in got.values())
+    assert got["kappa.npy"].shape == (1,) and got["kappa.npy"][0] == 2.5
+    with pytest.raises(SystemExit):
+        bench.write_outputs(str(tmp_path / "big"), {"q": np.zeros((bench.DUMP_LIMIT_BYTES // 8) + 1)})
+    assert not os.path.exists(tmp_path / "big" / "q.npy")
+
+
+def test_plain_and_full_options_exist():
+    import subprocess
+    import sys
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "--full" in r.stdout + r.stderr and "--dump-outputs" in r.stdout + r.stderr
+
+
+@pytest.mark.parametrize("cutgen", ["parallel", "deep"])
+def test_long_cut_streams_stay_valid(cutgen):
+    """Offsets that follow the ellipsoid's size: many more cuts than the first few hundred, replayed on the CPU oracle, all
+    succeed, every parallel cut stays parallel (b1^2 < tsq), and the predicted tsq stays close to the real one."""
+    import numpy as np
+    from ellalgo_rs_amd import synth
+    from oracle import oracle as orc
+    n, K = 512, 2500
+    kinds, grads, b0, b1 = bench.cut_stream(synth, cutgen, n, K)
+    _, _, r0, r1 = (synth.parallel_cuts if cutgen == "parallel" else synth.deep_cuts)(n, K)
+    o = orc.OracleEll.new_with_scalar(1.0, np.zeros(n))
+    ratios = []
+    for i in range(K):
+        assert o.update(int(kinds[i]), grads[i], float(b0[i]), None if np.isnan(b1[i]) else float(b1[i])) == 0, i
+        if cutgen == "parallel":
+            assert o.tsq > b1[i] ** 2, i          # o.tsq: the tsq cut i met
+        raw, got = (r1[i], b1[i]) if cutgen == "parallel" else (r0[i], b0[i])
+        if raw > 0:
+            ratios.append(o.tsq / (got / raw) ** 2)   # real tsq / predicted tsq, every cut
+    assert 0.75 < min(ratios) and max(ratios) < 1.05, (min(ratios), max(ratios))
+
+
+@pytest.mark.parametrize("cutgen,n", [("parallel", 301), ("deep", 256)])
+def test_cut_stream_is_synth_bit_for_bit(cutgen, n):
+    """The block generator builds exactly synth's cuts (gradients, kinds, offsets before the size tracking), across the
+    220-cut boundary of deep_cuts and for odd n."""
+    import numpy as np
+    from ellalgo_rs_amd import synth
+    K = 260
+    kinds, grads, b0, b1 = bench.cut_stream(synth, cutgen, n, K)
+    rk, rg, r0, r1 = (synth.parallel_cuts if cutgen == "parallel" else synth.deep_cuts)(n, K)
+    assert np.array_equal(kinds, rk) and np.array_equal(grads, rg)
+    t0, t1 = bench.track_tsq(n, rk, r0, r1)
+    assert np.array_equal(b0, t0) and np.array_equal(b1, t1, equal_nan=True)

@@ -1,10 +1,14 @@
-"""GPU: bench.py honours its output contract -- exactly ONE JSON line on stdout with the driver's fields, the
+"""GPU: bench.py honours its output contract -- exactly ONE JSON line on stdout with the driver's fields, and with --full the
 `roofline` object of the dominant kernel and the `cpu_baseline` object -- for the headline workload and for the
-secondary workloads."""
+secondary workloads; a plain run times its steps and nothing else, and --dump-outputs writes what they computed."""
+import importlib.util
 import json
 import os
 import subprocess
 import sys
+import time
+
+import numpy as np
 
 import pytest
 
@@ -13,6 +17,13 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 COMMON = {"metric": str, "value": float, "unit": str, "n_gpus": int, "steps": int, "warmup": int, "ms_per_step": float,
           "higher_is_better": bool, "scaling": str, "dtype": str, "data": str, "config": dict, "roofline": dict}
+
+
+def bench_module():
+    spec = importlib.util.spec_from_file_location("bench_dump", os.path.join(ROOT, "bench.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
 
 
 def run_bench(*args, timeout=900):
@@ -40,7 +51,7 @@ def check_common(d, steps, warmup):
 
 
 def test_headline_workload_contract():
-    d = run_bench("--steps", "16", "--warmup", "8", "--compare-steps", "0", "--profile-steps", "8", "--host-path-steps", "4",
+    d = run_bench("--full", "--steps", "16", "--warmup", "8", "--compare-steps", "0", "--profile-steps", "8", "--host-path-steps", "4",
                   "--cpu-budget", "2", "--live-loop-steps", "30")
     check_common(d, 16, 8)
     assert d["metric"].startswith("ellipsoid updates/sec at n=16384") and d["unit"] == "updates/s"
@@ -88,8 +99,61 @@ def test_headline_workload_contract():
                                            ("lowpass-n1024", ("--steps", "200", "--warmup", "50", "--profile-steps", "50")),
                                            ("batch-n16", ("--steps", "10", "--warmup", "2")),
                                            ("lmi-m1024-n128", ("--steps", "3", "--warmup", "1"))])
-def test_other_workloads_contract(workload, args):
-    d = run_bench("--workload", workload, "--cpu-budget", "1", "--host-path-steps", "0", *args)
+def test_other_workloads_contract(workload, args, tmp_path):
+    d = run_bench("--full", "--workload", workload, "--cpu-budget", "1", "--host-path-steps", "0", "--dump-outputs", str(tmp_path), *args)
     check_common(d, int(args[1]), int(args[3]))
     assert d["config"]["workload"] == workload
     assert d["cpu_baseline"]["kind"] == "port" and d["cpu_baseline"]["value"] > 0
+    dumped = [np.load(tmp_path / f) for f in os.listdir(tmp_path)]
+    assert dumped and all(a.dtype == np.float64 and a.size for a in dumped) and sum(a.nbytes for a in dumped) <= 64 << 20
+
+
+PLAIN_ONLY_FIELDS = ("cpu_baseline", "other_configs", "other_schedules", "host_call_path", "live_loop", "per_iteration_collective")
+
+
+def test_plain_run_times_its_steps_only_and_dumps_what_they_computed(tmp_path):
+    """The driver's form without --full: the contract fields, none of the extra legs, and a lean start (at most 30 s of the
+    whole process outside the warm-up and timed steps, the read-back of --dump-outputs included) at a step count that
+    fills a fraction of a second, where the set-up of every queued cut counts."""
+    K, W = 20000, 8
+    t0 = time.perf_counter()
+    d = run_bench("--gpus", "1", "--steps", str(K), "--warmup", str(W), "--dump-outputs", str(tmp_path))
+    wall = time.perf_counter() - t0
+    assert d["metric"].startswith("ellipsoid updates/sec at n=16384") and d["unit"] == "updates/s" and d["dtype"] == "f64"
+    assert d["higher_is_better"] is True and d["steps"] == K and d["warmup"] == W and d["config"]["workload"] == "n16384-parallel"
+    assert d["ms_per_step"] > 0 and abs(d["value"] - 1e3 / d["ms_per_step"]) < 1e-6 * d["value"]
+    assert not [k for k in PLAIN_ONLY_FIELDS if k in d] and d["roofline"]["per_kernel"] == {}
+    assert "steady_state_updates_per_s" not in d["config"]
+    assert wall - (K + W) * d["ms_per_step"] * 1e-3 < 30.0, wall
+    n = 16384
+    files = {f[:-4]: np.load(tmp_path / f) for f in os.listdir(tmp_path)}
+    assert set(files) == {"status", "tsq", "xc", "kappa", "q_diag", "q_sample"}
+    assert all(a.dtype == np.float64 for a in files.values()) and sum(a.nbytes for a in files.values()) <= 64 << 20
+    assert files["status"].shape == files["tsq"].shape == (K,) and np.all(files["status"] == 0) and np.all(files["tsq"] > 0)
+    assert files["xc"].shape == files["q_diag"].shape == (n,) and files["kappa"].shape == (1,) and files["q_sample"].shape == (1 << 20,)
+    assert np.all(np.isfinite(files["q_sample"])) and np.all(files["q_diag"] > 0) and np.any(files["xc"] != 0)
+
+
+def test_dumped_outputs_match_the_oracle(tmp_path, orc):
+    """--dump-outputs holds the state after the last timed step: n = 4096 deep cuts, warm-up + timed steps replayed on the CPU
+    oracle, to the north-star tolerance (1e-10 relative)."""
+    from ellalgo_rs_amd import synth
+    n, K, W = 4096, 20, 6
+    run_bench("--workload", "n4096-deep", "--steps", str(K), "--warmup", str(W), "--dump-outputs", str(tmp_path))
+    got = {f[:-4]: np.load(tmp_path / f) for f in os.listdir(tmp_path)}
+    kinds, grads, b0, b1 = bench_module().cut_stream(synth, "deep", n, W + K)
+    o = orc.OracleEll.new_with_scalar(1.0, np.zeros(n))
+    tsq = []
+    for i in range(W + K):
+        assert o.update(int(kinds[i]), grads[i], float(b0[i]), None if np.isnan(b1[i]) else float(b1[i])) == 0
+        tsq.append(o.tsq)
+    mq = o.mq
+    assert np.all(got["status"] == 0)
+    assert np.max(np.abs(got["tsq"] - tsq[W:]) / np.abs(tsq[W:])) <= 1e-10
+    assert np.max(np.abs(got["xc"] - o.xc)) <= 1e-10 * np.max(np.abs(o.xc))
+    assert abs(got["kappa"][0] - o.kappa) <= 1e-10 * abs(o.kappa)
+    assert np.max(np.abs(got["q_diag"] - np.diagonal(mq))) <= 1e-10 * np.max(np.abs(mq))
+    # n^2 = 2^24 entries: the seeded sample of 2^20 of them, the same positions bench.dump_sample takes from the oracle's matrix
+    want = bench_module().dump_sample(mq)
+    assert got["q_sample"].shape == want.shape == (1 << 20,)
+    assert np.max(np.abs(got["q_sample"] - want)) <= 1e-10 * np.max(np.abs(mq))

@@ -7,13 +7,13 @@ O=$R/gpurun_out
 mkdir -p $O
 cd $R
 if [ -z "$PROFILES_ONLY" ]; then
-python bench.py > $O/bench_n16384.json 2> $O/bench_n16384.err
+python bench.py --full > $O/bench_n16384.json 2> $O/bench_n16384.err
 for w in n8192-deep n32768-deep n4096-deep; do
-  python bench.py --workload $w --no-cpu-baseline > $O/bench_$w.json 2>/dev/null
+  python bench.py --full --workload $w --no-cpu-baseline > $O/bench_$w.json 2>/dev/null
 done
 fi
 export TMPDIR=/tmp
-ARGS="bench.py --steps 64 --warmup 16 --compare-steps 0 --host-path-steps 0 --no-cpu-baseline"
+ARGS="bench.py --full --steps 64 --warmup 16 --compare-steps 0 --host-path-steps 0 --no-cpu-baseline"
 cd /tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_stats -- python3 $R/$ARGS > $O/prof_stats.json 2> $O/prof_stats.err
 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/prof_fetch -- python3 $R/$ARGS > /dev/null 2> $O/prof_fetch.err

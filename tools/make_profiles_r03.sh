@@ -8,18 +8,18 @@ O=$R/gpurun_out/r3prof
 mkdir -p $O
 export TMPDIR=/tmp
 cd /tmp
-python3 $R/bench.py > $O/bench_default.json 2> $O/bench_default.err
+python3 $R/bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 echo "bench done"
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/default_stats -- python3 $R/bench.py > $O/bench_default_profiled_run.json 2> $O/default_stats.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/default_stats -- python3 $R/bench.py --full > $O/bench_default_profiled_run.json 2> $O/default_stats.err
 echo "stats done"
 H="--other-configs off --steps 64 --warmup 16 --compare-steps 0 --host-path-steps 0 --no-cpu-baseline"
-rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/n16384_fetch -- python3 $R/bench.py $H > /dev/null 2> $O/n16384_fetch.err
-rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/n16384_write -- python3 $R/bench.py $H > /dev/null 2> $O/n16384_write.err
+rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/n16384_fetch -- python3 $R/bench.py --full $H > /dev/null 2> $O/n16384_fetch.err
+rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/n16384_write -- python3 $R/bench.py --full $H > /dev/null 2> $O/n16384_write.err
 echo "headline pmc done"
 W="--workload n4096-deep --steps 200 --warmup 20 --compare-steps 0 --host-path-steps 0 --no-cpu-baseline"
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/n4096_stats -- python3 $R/bench.py $W > $O/bench_n4096_profiled_run.json 2> $O/n4096_stats.err
-rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/n4096_fetch -- python3 $R/bench.py $W > /dev/null 2> $O/n4096_fetch.err
-rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/n4096_write -- python3 $R/bench.py $W > /dev/null 2> $O/n4096_write.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/n4096_stats -- python3 $R/bench.py --full $W > $O/bench_n4096_profiled_run.json 2> $O/n4096_stats.err
+rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/n4096_fetch -- python3 $R/bench.py --full $W > /dev/null 2> $O/n4096_fetch.err
+rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/n4096_write -- python3 $R/bench.py --full $W > /dev/null 2> $O/n4096_write.err
 echo "n4096 done"
 cd $R
 python tools/pmc_summary.py $O/default_stats $O/n16384_fetch $O/n16384_write $O/summary_n16384 bench_n16384 n16384-parallel || true

@@ -16,22 +16,22 @@ cd /tmp
 for S in $STAGES; do
 case $S in
 bench)
-  python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_form_steps20.json 2> $O/bench_driver_form.err
-  python3 $R/bench.py > $O/bench_default_all_configs.json 2> $O/bench_default.err
+  python3 $R/bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_form_steps20.json 2> $O/bench_driver_form.err
+  python3 $R/bench.py --full > $O/bench_default_all_configs.json 2> $O/bench_default.err
   echo "bench done";;
 stats)
-  rocprofv3 --kernel-trace --stats --output-format csv -d $O/driver_stats -- python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_form_profiled_run.json 2> $O/driver_stats.err || true
+  rocprofv3 --kernel-trace --stats --output-format csv -d $O/driver_stats -- python3 $R/bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_form_profiled_run.json 2> $O/driver_stats.err || true
   echo "stats done";;
 pmc)
   H="--other-configs off --steps 64 --warmup 16 --compare-steps 0 --host-path-steps 0 --live-loop-steps 0 --no-cpu-baseline"
-  rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/n16384_fetch -- python3 $R/bench.py $H > /dev/null 2> $O/n16384_fetch.err || true
-  rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/n16384_write -- python3 $R/bench.py $H > /dev/null 2> $O/n16384_write.err || true
+  rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/n16384_fetch -- python3 $R/bench.py --full $H > /dev/null 2> $O/n16384_fetch.err || true
+  rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/n16384_write -- python3 $R/bench.py --full $H > /dev/null 2> $O/n16384_write.err || true
   echo "headline pmc done";;
 stable)
   W="--workload n16384-ellstable --steps 48 --warmup 8 --host-path-steps 0 --live-loop-steps 0 --no-cpu-baseline"
-  rocprofv3 --kernel-trace --stats --output-format csv -d $O/stable_stats -- python3 $R/bench.py $W > $O/bench_ellstable_profiled_run.json 2> $O/stable_stats.err || true
-  rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/stable_fetch -- python3 $R/bench.py $W > /dev/null 2> $O/stable_fetch.err || true
-  rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/stable_write -- python3 $R/bench.py $W > /dev/null 2> $O/stable_write.err || true
+  rocprofv3 --kernel-trace --stats --output-format csv -d $O/stable_stats -- python3 $R/bench.py --full $W > $O/bench_ellstable_profiled_run.json 2> $O/stable_stats.err || true
+  rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/stable_fetch -- python3 $R/bench.py --full $W > /dev/null 2> $O/stable_fetch.err || true
+  rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/stable_write -- python3 $R/bench.py --full $W > /dev/null 2> $O/stable_write.err || true
   echo "ellstable done";;
 esac
 done

@@ -8,7 +8,7 @@ mkdir -p $O
 export TMPDIR=/tmp
 cd /tmp
 H="--other-configs off --steps 96 --warmup 48 --compare-steps 0 --host-path-steps 0 --live-loop-steps 0 --no-cpu-baseline"
-rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES SQ_WAIT_INST_LDS SQ_BUSY_CYCLES --kernel-trace --output-format csv -d $O/sq -- python3 $R/bench.py $H > /dev/null 2> $O/sq.err || true
+rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES SQ_WAIT_INST_LDS SQ_BUSY_CYCLES --kernel-trace --output-format csv -d $O/sq -- python3 $R/bench.py --full $H > /dev/null 2> $O/sq.err || true
 cd $R
 python3 - <<PY
 import collections, csv, glob

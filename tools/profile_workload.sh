@@ -7,7 +7,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out
 mkdir -p $O
 export TMPDIR=/tmp
-ARGS="bench.py --workload $W --steps 64 --warmup 16 --compare-steps 0 --host-path-steps 0 --no-cpu-baseline $*"
+ARGS="bench.py --full --workload $W --steps 64 --warmup 16 --compare-steps 0 --host-path-steps 0 --no-cpu-baseline $*"
 cd /tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/${TAG}_stats -- python3 $R/$ARGS > $O/${TAG}_profiled_run.json 2> $O/${TAG}_stats.err
 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/${TAG}_fetch -- python3 $R/$ARGS > /dev/null 2> $O/${TAG}_fetch.err
