@@ -55,6 +55,12 @@ EXPORTS = [
     "ellhip_sharded_create_custom", "ellhip_sharded_set_collective",
 ]
 
+# every symbol include/ellhip_svm.h declares (kept apart from EXPORTS, which lists the other five headers)
+SVM_EXPORTS = [
+    "ellhip_svm_create", "ellhip_svm_destroy", "ellhip_svm_assess_optim", "ellhip_svm_margins", "ellhip_svm_last",
+    "ellhip_svm_optim",
+]
+
 
 class EllHipError(RuntimeError):
     pass
@@ -245,8 +251,15 @@ def load():
         "ellhip_shards_exchange": (i32, [vp, i32]),
         "ellhip_sharded_create_custom": (i32, [C.POINTER(vp), i64, dbl, vp, vp, vp, i32, i32, i32, i32, i32, vp, vp, vp]),
         "ellhip_sharded_set_collective": (i32, [vp, vp, vp, vp]),
+        # include/ellhip_svm.h
+        "ellhip_svm_create": (i32, [C.POINTER(vp), i64, i64, vp, vp, i32]),
+        "ellhip_svm_destroy": (None, [vp]),
+        "ellhip_svm_assess_optim": (i32, [vp, vp, C.POINTER(dbl), vp, C.POINTER(dbl), C.POINTER(i32)]),
+        "ellhip_svm_margins": (i32, [vp, vp, vp]),
+        "ellhip_svm_last": (i32, [vp, C.POINTER(i64), C.POINTER(dbl)]),
+        "ellhip_svm_optim": (i32, [vp, vp, C.POINTER(dbl), i64, dbl, vp, C.POINTER(i32), C.POINTER(i64)]),
     }
-    for name in EXPORTS:
+    for name in EXPORTS + SVM_EXPORTS:
         fn = getattr(L, name)  # AttributeError if the library does not export it
         fn.restype, fn.argtypes = sig[name]
     _lib = L

@@ -9,6 +9,7 @@
 #include <thread>
 
 #include "lowpass_kernels.hpp"
+#include "device_loop.inc.hpp"
 
 struct ellhip_lowpass {
     int device = 0;
@@ -108,118 +109,55 @@ int lp_assess_host(ellhip_lowpass* o, int mode, const double* x, double* gamma_i
     return 1;
 }
 
-// One device-resident loop: mode 1 = cutting_plane_optim (src/cutting_plane.rs:286-313), 0 = cutting_plane_feas
-// (:205-227).  Iterations are enqueued in batches; every kernel of an iteration (oracle scan, oracle
-// finish, GEMV, scalar stage, shrink) is a no-op once the loop has halted on the device, so the host
-// looks at the state once per batch only.
+// The oracle's side of the device-resident loop (device_loop.inc.hpp): mode 1 = cutting_plane_optim
+// (src/cutting_plane.rs:286-313), 0 = cutting_plane_feas (:205-227).
+struct LpStage {
+    ellhip_lowpass* o;
+    int mode;
+    double* gamma_inout;
+    double* x_best_out;
+    int* has_best_out;
+    int64_t* niter_out;
+
+    hipStream_t stream() { return o->stream; }
+    const double* grad() { return o->d_g; }
+    const CutParams* cut() { return o->d_cp; }
+    int begin(hipStream_t st) {
+        HIPCHK(hipMemcpyAsync(o->h_ls, o->d_ls, sizeof(LpState), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        o->h_ls->has_best = 0;
+        o->h_ls->error = 0;
+        if (mode == 1) o->h_ls->sp_sq = *gamma_inout;
+        HIPCHK(hipMemcpyAsync(o->d_ls, o->h_ls, sizeof(LpState), hipMemcpyHostToDevice, st));
+        HIPCHK(hipStreamSynchronize(st));
+        return 0;
+    }
+    int issue(hipStream_t st, ellhip_space* s, const int* halted) {
+        return lp_issue(o, st, s->d_xc, mode, s->d_st, halted, s);
+    }
+    int finish(hipStream_t st, long long niter) {
+        HIPCHK(hipMemcpyAsync(o->h_ls, o->d_ls, sizeof(LpState), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        if (o->h_ls->error)
+            return fail(ELLHIP_E_STATE, "lowpass oracle: feasible point without a stopband maximum (kmax = -1)");
+        *niter_out = niter;
+        *has_best_out = o->h_ls->has_best;
+        if (o->h_ls->has_best && x_best_out) {
+            HIPCHK(hipMemcpyAsync(o->h_vec, o->d_xbest, (size_t)o->P.n * sizeof(double), hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));
+            memcpy(x_best_out, o->h_vec, (size_t)o->P.n * sizeof(double));
+        }
+        if (mode == 1) *gamma_inout = o->h_ls->sp_sq;
+        return 0;
+    }
+};
+
 int lp_drive(ellhip_space* s, ellhip_lowpass* o, int mode, double* gamma_inout, long long max_iters, double tol,
              double* x_best_out, int* has_best_out, int64_t* niter_out) {
     if (!s || !o || !has_best_out || !niter_out || (mode == 1 && !gamma_inout))
         return fail(ELLHIP_E_INVALID, "NULL argument");
-    if (s->n != o->P.n) return fail(ELLHIP_E_INVALID, "oracle and search space dimensions differ");
-    if (s->device != o->device) return fail(ELLHIP_E_INVALID, "oracle and search space live on different devices");
-    if (s->sharded) return fail(ELLHIP_E_INVALID, "device-resident loops need an unsharded search space");
-    if (max_iters < 0) return fail(ELLHIP_E_INVALID, "max_iters < 0");
-    DeviceGuard guard(s->device);
-    int rc = ensure_committed(s);
-    if (rc) return rc;
-    drop_prime(s);
-    HIPCHK(hipStreamSynchronize(o->stream));
-    hipStream_t st = s->stream;
-    // loop state on the device: tolerance, iteration counter, stop reason; the oracle's gamma
-    rc = read_back(s);
-    if (rc) return rc;
-    s->h_result->tol = tol;
-    s->h_result->niter = 0;
-    s->h_result->stop = STOP_NONE;
-    s->h_result->halted = 0;
-    HIPCHK(hipMemcpyAsync(s->d_st, s->h_result, sizeof(DevState), hipMemcpyHostToDevice, st));
-    HIPCHK(hipMemcpyAsync(o->h_ls, o->d_ls, sizeof(LpState), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    o->h_ls->has_best = 0;
-    o->h_ls->error = 0;
-    if (mode == 1) o->h_ls->sp_sq = *gamma_inout;
-    HIPCHK(hipMemcpyAsync(o->d_ls, o->h_ls, sizeof(LpState), hipMemcpyHostToDevice, st));
-    HIPCHK(hipStreamSynchronize(st));
-
-    int* d_halted = reinterpret_cast<int*>(reinterpret_cast<char*>(s->d_st) + offsetof(DevState, halted));
-    const long long BATCH = 64;
-    std::vector<int> slot_of((size_t)BATCH);
-    long long done = 0;
-    CutParams none{};
-    bool stopped = false;
-    while (done < max_iters && !stopped) {
-        const long long nb = (max_iters - done < BATCH) ? max_iters - done : BATCH;
-        for (long long i = 0; i < nb; ++i) {
-            // oracle at the current centre; for every iteration but the first of a batch it runs between the
-            // scalar stage of the previous cut and that cut's shrink, which then carries this cut's GEMV
-            rc = lp_issue(o, st, s->d_xc, mode, s->d_st, d_halted, s);
-            if (rc) return rc;
-            if (s->shrink_pending || (deferring(s) && i > 0)) {
-                rc = do_commit(s, s->shrink_pending, o->d_g);
-                if (rc) return rc;
-                s->shrink_pending = false;
-                s->cur ^= 1;
-            } else {
-                rc = do_prime(s, o->d_g, s->cur);
-                if (rc) return rc;
-            }
-            slot_of[(size_t)i] = s->cur;
-            rc = do_cut(s, o->d_g, o->d_cp, none, 1, nullptr, nullptr);
-            if (rc) return rc;
-            s->shrink_pending = s->variant == ELLHIP_SPACE_ELL && !deferring(s);
-        }
-        // end of batch: apply the last shrink (it has no next gradient yet), then look at the loop state
-        rc = do_commit(s, s->shrink_pending, nullptr);
-        if (rc) return rc;
-        s->shrink_pending = false;
-        rc = read_back(s);
-        if (rc) return rc;
-        const DevState hs = *s->h_result;
-        if (s->needs_mirror && (hs.niter > 0 || hs.stop == STOP_TOL)) s->needs_mirror = false;
-        if (hs.halted) {
-            stopped = true;
-            const long long at = hs.niter - done;  // index of the stopping iteration inside this batch
-            if (s->variant == ELLHIP_SPACE_ELL) s->npend = hs.npend;
-            // clear the halt so that the space is usable again (and so that the shrink below runs)
-            s->h_result->halted = 0;
-            HIPCHK(hipMemcpyAsync(s->d_st, s->h_result, sizeof(DevState), hipMemcpyHostToDevice, st));
-            if (hs.stop == STOP_TOL && s->variant == ELLHIP_SPACE_ELL && !deferring(s)) {
-                // src/cutting_plane.rs:308 tests tsq AFTER the update: the update that hit the tolerance is
-                // complete in the reference.  Its scalar stage set `halted`, which turned the shrink pass into a
-                // no-op; gt of that cut is still in its slot and DevState.apply is still 1.
-                if (at < 0 || at >= nb) return fail(ELLHIP_E_STATE, "lowpass driver: inconsistent iteration count");
-                s->cur = slot_of[(size_t)at];
-                rc = do_commit(s, true, nullptr);
-                if (rc) return rc;
-            }
-            HIPCHK(hipStreamSynchronize(st));
-        }
-        done += nb;
-    }
-    drop_prime(s);
-    rc = read_back(s);
-    if (rc) return rc;
-    // results
-    HIPCHK(hipMemcpyAsync(o->h_ls, o->d_ls, sizeof(LpState), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (o->h_ls->error)
-        return fail(ELLHIP_E_STATE, "lowpass oracle: feasible point without a stopband maximum (kmax = -1)");
-    *niter_out = stopped ? s->h_result->niter : max_iters;
-    *has_best_out = o->h_ls->has_best;
-    if (o->h_ls->has_best && x_best_out) {
-        HIPCHK(hipMemcpyAsync(o->h_vec, o->d_xbest, (size_t)o->P.n * sizeof(double), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        memcpy(x_best_out, o->h_vec, (size_t)o->P.n * sizeof(double));
-    }
-    if (mode == 1) *gamma_inout = o->h_ls->sp_sq;
-    // plain queues and direct updates do not test a tolerance
-    s->h_result->tol = -1.0;
-    s->h_result->stop = STOP_NONE;
-    s->h_result->niter = 0;
-    HIPCHK(hipMemcpyAsync(s->d_st, s->h_result, sizeof(DevState), hipMemcpyHostToDevice, st));
-    HIPCHK(hipStreamSynchronize(st));
-    return 0;
+    LpStage stage{o, mode, gamma_inout, x_best_out, has_best_out, niter_out};
+    return drive_device_loop(s, stage, o->P.n, o->device, max_iters, tol);
 }
 
 }  // namespace
