@@ -1355,6 +1355,190 @@ __global__ __launch_bounds__(256, 2) void k_symm_mfma_q2(const double* __restric
     }
 }
 
+// ----------------------------------------------------------------------------- k_apply_symm_q ---
+// The apply pass of NP recorded updates and the NEXT group's product pass in one sweep over the lower triangle: k_apply_mfma<NP>
+// writes every block of it and k_symm_mfma_q / _q2 read all of it back right after (8 n^2 + 4 n^2 bytes per cycle instead of
+// 8 n^2 + 4 n^2 + 4 n^2).  Tiles, their queue and the wave -> 16-column-block map are the product pass'; per block:
+//   1. x[16] = the block as symm_tile loads it.  x[4 q .. 4 q + 3] (rows 16 q + (lane >> 4) + 4 i, column lane & 15) is the C / D
+//      operand of the 16 x 16 x 4 f64 MFMA for the row group q, so the update runs on the loaded registers:
+//          x += sum_s A_q,s B_s,   A[r][k] = -(c_k v_k[r])  (LDS, staged per tile),   B[k][c] = v_k[c]  (pend),
+//      k = 4 s + (lane >> 4), s = 0 .. NP / 4 - 1 in order: k_apply_mfma's operands in k_apply_mfma's order for every element
+//      (which of its 16 x 16 tiles an element sits in does not enter), so the updated block is bit-identical to that pass' result;
+//   2. the block goes back to Q;
+//   3. the column and row products of symm_tile (WIDE = false, gT[c][16]) / symm_tile2 (WIDE = true, gT[c][32]) run on the
+//      updated registers -- the values the separate pass would load -- with the same masks, LDS transposition and wave order:
+//      rowpart / colpart bit-identical as well.
+// k_apply_mfma applies whether or not the queue has halted (updates recorded before the failing cut are owed); the product
+// kernels do nothing once it has.  Here: the update always, the products only while st->halted is clear.
+// Unsharded handles only (row0 = 0, n % 64 == 0: every strip full, so k_apply_mfma's row and column limits never cut a block).
+// LDS: sh (34 KiB) + sgr (16.5 KiB) + the strip's A operands (64 NP doubles: 24 KiB at NP = 48) -- two workgroups per CU.
+template <int NP, bool NT, int SEG, bool WIDE>
+__device__ __forceinline__ void apply_symm_tile(double* __restrict__ Q, long long ld, long long n, long long I, long long J,
+                                                const double* __restrict__ pend, const double* __restrict__ cpend,
+                                                const double* __restrict__ gT, int lv, double* __restrict__ rowpart,
+                                                double* __restrict__ colpart, long long rowpart_stride, long long colpart_stride,
+                                                bool prod, double (*sh)[SYMV_H * SMM_PITCH], double (*sgr)[SMM_NV2 + 1],
+                                                double* __restrict__ sa) {
+    constexpr int KS = NP / 4;
+    constexpr int NVT = WIDE ? 2 : 1;      // 16-wide column tiles of the product
+    constexpr int NVW = SMM_NV * NVT;      // row pitch of gT
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int lr = lane >> 4, lc = lane & 15;
+    const long long r0 = I * SYMV_H;
+    const long long c0 = J * SEG;
+    const bool full = c0 + SEG - 1 < r0;
+    // A operands of the strip, sa[((q KS / 2 + s / 2) 64 + lane) 2 + (s & 1)] = A[16 q + (lane & 15)][4 s + (lane >> 4)]: one
+    // 16-byte LDS read gives a lane the operands of two consecutive k-steps
+    for (int e = threadIdx.x; e < 4 * KS * 64; e += 256) {
+        const int q = e / (KS * 64), s = (e / 64) % KS, ln = e % 64;
+        const int k = 4 * s + (ln >> 4);
+        sa[((q * (KS / 2) + s / 2) * 64 + ln) * 2 + (s & 1)] = -(cpend[k] * pend[(long long)k * n + r0 + 16 * q + (ln & 15)]);
+    }
+    if (prod)
+        for (int k = threadIdx.x; k < SYMV_H * NVW; k += 256) sgr[k / NVW][k % NVW] = gT[(r0 + k / NVW) * NVW + k % NVW];
+    __syncthreads();
+    double4_t dr[NVT][4];
+#pragma unroll
+    for (int t = 0; t < NVT; ++t)
+#pragma unroll
+        for (int jj = 0; jj < 4; ++jj) dr[t][jj] = double4_t{0.0, 0.0, 0.0, 0.0};
+    const long long cend = (c0 + SEG < r0 + SYMV_H) ? c0 + SEG : r0 + SYMV_H;
+    const int nblk = (int)((cend - c0) / 16);
+    double* mysh = sh[wave];
+    double* qbase = Q + (r0 + lr) * ld + lc;
+    const double* pbase = pend + (long long)lr * n + lc;
+    for (int b = wave; b < nblk; b += 4) {
+        const long long cb = c0 + 16 * (long long)b;
+        double x[16], bv[KS], gc[NVT][4];
+#pragma unroll
+        for (int j = 0; j < 16; ++j) x[j] = ld_stream<NT, double>(qbase + (long long)(4 * j) * ld + cb);
+#pragma unroll
+        for (int s = 0; s < KS; ++s) bv[s] = pbase[(long long)(4 * s) * n + cb];
+        // (the phases are kept apart: with the row-sum accumulators live across the loop, 256 registers hold one phase's
+        // operands at a time, not the scheduler's hoisted loads of all three)
+        __builtin_amdgcn_sched_barrier(0);
+        // 1. the recorded updates, four row groups side by side
+        double4_t acc[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) acc[q] = double4_t{x[4 * q], x[4 * q + 1], x[4 * q + 2], x[4 * q + 3]};
+#pragma unroll
+        for (int s2 = 0; s2 < KS / 2; ++s2)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const double2_t a = *reinterpret_cast<const double2_t*>(&sa[((q * (KS / 2) + s2) * 64 + lane) * 2]);
+                acc[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(a.x, bv[2 * s2], acc[q], 0, 0, 0);
+                acc[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(a.y, bv[2 * s2 + 1], acc[q], 0, 0, 0);
+                if (q == 3) __builtin_amdgcn_sched_barrier(0);
+            }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            x[4 * q] = acc[q].x;
+            x[4 * q + 1] = acc[q].y;
+            x[4 * q + 2] = acc[q].z;
+            x[4 * q + 3] = acc[q].w;
+        }
+        // 2. back to Q (default policy, as k_apply_mfma stores)
+#pragma unroll
+        for (int j = 0; j < 16; ++j) qbase[(long long)(4 * j) * ld + cb] = x[j];
+        if (!prod) continue;  // (uniform)
+        __builtin_amdgcn_sched_barrier(0);
+        // 3. the products, as symm_tile2 forms them
+#pragma unroll
+        for (int t = 0; t < NVT; ++t)
+#pragma unroll
+            for (int kb = 0; kb < 4; ++kb) gc[t][kb] = gT[(cb + 4 * kb + lr) * NVW + 16 * t + lc];
+        const bool diag = !full && cb + 15 >= r0;
+        double4_t dc[NVT];
+#pragma unroll
+        for (int t = 0; t < NVT; ++t) {
+            dc[t] = double4_t{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+            for (int j = 0; j < 16; ++j) {
+                const long long r = r0 + 4 * j + lr, c = cb + lc;
+                const double below = (!diag || c < r) ? x[j] : 0.0;  // column sums: strictly below the diagonal
+                dc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(sgr[4 * j + lr][16 * t + lc], below, dc[t], 0, 0, 0);
+            }
+        }
+        if (diag) {
+#pragma unroll
+            for (int j = 0; j < 16; ++j) {
+                const long long r = r0 + 4 * j + lr, c = cb + lc;
+                x[j] = (c <= r) ? x[j] : 0.0;  // row sums: the diagonal counts once, here
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 16; ++j) mysh[(4 * j + lr) * SMM_PITCH + lc] = x[j];
+#pragma unroll
+        for (int t = 0; t < NVT; ++t)
+#pragma unroll
+            for (int jj = 0; jj < 4; ++jj)
+#pragma unroll
+                for (int kb = 0; kb < 4; ++kb) {
+                    const double tv = mysh[(16 * jj + lc) * SMM_PITCH + 4 * kb + lr];
+                    dr[t][jj] = __builtin_amdgcn_mfma_f64_16x16x4f64(gc[t][kb], tv, dr[t][jj], 0, 0, 0);
+                }
+#pragma unroll
+        for (int t = 0; t < NVT; ++t) {
+            const double o[4] = {dc[t].x, dc[t].y, dc[t].z, dc[t].w};
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int v = 16 * t + lr + 4 * i;
+                if (v < lv) colpart[(long long)v * colpart_stride + I * n + cb + lc] = o[i];
+            }
+        }
+    }
+    if (!prod) return;
+    __syncthreads();
+    double* red = &sh[0][0];
+#pragma unroll
+    for (int t = 0; t < NVT; ++t) {
+#pragma unroll
+        for (int jj = 0; jj < 4; ++jj) {
+            const double o[4] = {dr[t][jj].x, dr[t][jj].y, dr[t][jj].z, dr[t][jj].w};
+#pragma unroll
+            for (int i = 0; i < 4; ++i) red[((wave * 4 + jj) * 4 + i) * 64 + lane] = o[i];
+        }
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int v = 16 * t + lr + 4 * i;
+            const int jj = wave;
+            const double s0 = red[((0 * 4 + jj) * 4 + i) * 64 + lane], s1 = red[((1 * 4 + jj) * 4 + i) * 64 + lane];
+            const double s2 = red[((2 * 4 + jj) * 4 + i) * 64 + lane], s3 = red[((3 * 4 + jj) * 4 + i) * 64 + lane];
+            if (v < lv) rowpart[(long long)v * rowpart_stride + J * n + r0 + 16 * jj + lc] = ((s0 + s1) + s2) + s3;
+        }
+        __syncthreads();
+    }
+}
+
+template <int NP, bool NT, int SEG, bool WIDE>
+__global__ __launch_bounds__(256, 2) void k_apply_symm_q(double* __restrict__ Q, long long ld, long long n,
+                                                         const double* __restrict__ pend, const double* __restrict__ cpend,
+                                                         const double* __restrict__ gT, int lv, double* __restrict__ rowpart,
+                                                         double* __restrict__ colpart, long long rowpart_stride,
+                                                         long long colpart_stride, const DevState* __restrict__ st,
+                                                         const SymmTile* __restrict__ tiles, int ntiles,
+                                                         unsigned* __restrict__ queue) {
+    static_assert(NP % 8 == 0, "k-steps taken in pairs");
+    __shared__ double sh[4][SYMV_H * SMM_PITCH];
+    __shared__ double sgr[SYMV_H][SMM_NV2 + 1];
+    __shared__ double sa[SYMV_H * NP];
+    __shared__ int s_t;
+    const bool prod = !st->halted;  // (the update is owed either way)
+    for (;;) {
+        __syncthreads();  // (everybody has read the previous index and is done with the tile's LDS)
+        if (threadIdx.x == 0) {
+            const unsigned t = atomicAdd(queue, 1u);
+            s_t = t < (unsigned)ntiles ? (int)t : -1;
+        }
+        __syncthreads();
+        const int t = s_t;
+        if (t < 0) return;  // (uniform)
+        apply_symm_tile<NP, NT, SEG, WIDE>(Q, ld, n, (long long)tiles[t].I, (long long)tiles[t].J, pend, cpend, gT, lv, rowpart,
+                                           colpart, rowpart_stride, colpart_stride, prod, sh, sgr, sa);
+    }
+}
+
 // ----------------------------------------------------------------------------------- k_publish ---
 // The live SearchSpace loop (src/cutting_plane.rs:299-311: xc() -> oracle -> update_*_cut) needs, after every update, the
 // cut's status / tsq (the caller's next branch, :308) and the new centre (the oracle's next argument, :300) -- and nothing

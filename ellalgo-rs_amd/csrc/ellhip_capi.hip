@@ -82,6 +82,7 @@ struct Defaults {
     int overlap = 1;           // ELLHIP_OPT_OVERLAP
     int lookahead = 32;        // ELLHIP_OPT_LOOKAHEAD
     int queue_depth = 48;      // ELLHIP_OPT_QUEUE_DEPTH
+    int apply_symm = 1;        // ELLHIP_OPT_APPLY_SYMM
     int stable_solve = 3;      // ELLHIP_OPT_STABLE_SOLVE
     int stable_factor = 2;     // ELLHIP_OPT_STABLE_FACTOR
     int pad = -1;              // ELLHIP_OPT_PAD: extra doubles per row of Q; -1 = by size (create_impl)
@@ -148,6 +149,7 @@ struct ellhip_space {
     // ELLHIP_OPT_LOOKAHEAD): vector l of a group writes partial-sum set 2 + l (slices of one allocation)
     int lookahead = 32;
     int queue_depth = 48;            // recorded updates a queue run on the group stage lets pile up before an apply pass (0: the handle's depth)
+    int apply_symm = 1;              // that apply pass rides on the next group's product pass (k_apply_symm_q; queue_run_multi)
     double* d_rowpart_m = nullptr;   // [MULTI_MAX][nsegs][n]
     double* d_colpart_m = nullptr;   // [MULTI_MAX][nstrips][n]
     double* d_gT = nullptr;          // [n][16]: a group's gradients side by side (operand layout of k_symm_mfma)
@@ -337,6 +339,7 @@ void pick_shape(ellhip_space* s) {
     s->overlap = g_defaults.overlap;
     s->lookahead = g_defaults.lookahead;
     s->queue_depth = g_defaults.queue_depth;
+    s->apply_symm = g_defaults.apply_symm;
     s->resident = g_defaults.resident;
     s->stable_solve = g_defaults.stable_solve;
     s->stable_factor = g_defaults.stable_factor;
@@ -447,6 +450,14 @@ bool symv_ok(const ellhip_space* s);
 // While the GEMVs of this handle read the lower triangle only (symv_ok), so does the apply pass: half the
 // traffic; the strict upper triangle goes stale until make_q_current() mirrors it back.
 int side_join(ellhip_space* s);
+// (after an apply pass: forget the recorded updates)
+int pend_reset(ellhip_space* s) {
+    hipLaunchKernelGGL(k_pend_reset, dim3(64), dim3(256), 0, s->stream, s->d_pend, s->d_cpend,
+                       (long long)(s->npend > s->defer ? MAXPEND : s->defer) * s->n, s->d_st);
+    HIPCHK(hipGetLastError());
+    s->npend = 0;
+    return 0;
+}
 int flush_pending(ellhip_space* s, const double* gvec, double* gv_out) {
     {
         int jrc = side_join(s);  // a writer of Q: nothing issued ahead on the second stream may still be reading it
@@ -502,11 +513,7 @@ int flush_pending(ellhip_space* s, const double* gvec, double* gv_out) {
         HIPCHK(hipGetLastError());
         s->dir ^= 1;
     }
-    hipLaunchKernelGGL(k_pend_reset, dim3(64), dim3(256), 0, s->stream, s->d_pend, s->d_cpend,
-                       (long long)(s->npend > s->defer ? MAXPEND : s->defer) * s->n, s->d_st);
-    HIPCHK(hipGetLastError());
-    s->npend = 0;
-    return 0;
+    return pend_reset(s);
 }
 
 int launch_mirror_if_needed(ellhip_space* s) {
@@ -1666,6 +1673,27 @@ int multi_setup(ellhip_space* s) {
             ELLHIP_SYMM_WARM(k_symm_mfma_q2<false, SYMV_SEG_SMALL>);
         }
 #undef ELLHIP_SYMM_WARM
+        // (and the fused apply + product passes, ELLHIP_OPT_APPLY_SYMM)
+#define ELLHIP_APPLY_SYMM_WARM(...)                                                                                                  \
+    hipLaunchKernelGGL((__VA_ARGS__), dim3(1), dim3(256), 0, s->stream, s->d_Q, s->ld, s->n, (const double*)s->d_pend,               \
+                       (const double*)s->d_cpend, (const double*)s->d_gT, 0, s->d_rowpart_m, s->d_colpart_m,                         \
+                       (long long)rowpart_elems(s), (long long)colpart_elems(s), (const DevState*)s->d_st,                         \
+                       (const SymmTile*)s->d_symm_tiles, 0, s->d_symm_queue)
+#define ELLHIP_APPLY_SYMM_WARM4(NTV, SEGV)                         \
+    do {                                                           \
+        ELLHIP_APPLY_SYMM_WARM(k_apply_symm_q<MAXPEND, NTV, SEGV, true>);  \
+        ELLHIP_APPLY_SYMM_WARM(k_apply_symm_q<MAXPEND, NTV, SEGV, false>); \
+        ELLHIP_APPLY_SYMM_WARM(k_apply_symm_q<24, NTV, SEGV, true>);       \
+        ELLHIP_APPLY_SYMM_WARM(k_apply_symm_q<24, NTV, SEGV, false>);      \
+    } while (0)
+        if (s->row0 == 0 && !s->sharded) {
+            if (wide && nt) ELLHIP_APPLY_SYMM_WARM4(true, SYMV_SEG);
+            else if (wide) ELLHIP_APPLY_SYMM_WARM4(false, SYMV_SEG);
+            else if (nt) ELLHIP_APPLY_SYMM_WARM4(true, SYMV_SEG_SMALL);
+            else ELLHIP_APPLY_SYMM_WARM4(false, SYMV_SEG_SMALL);
+        }
+#undef ELLHIP_APPLY_SYMM_WARM4
+#undef ELLHIP_APPLY_SYMM_WARM
         HIPCHK(hipGetLastError());
     }
     return 0;
@@ -1741,6 +1769,75 @@ void symm_mfma_go(ellhip_space* s, const double* g_dev, int lv, hipStream_t st, 
     }
 #undef ELLHIP_SYMM_Q
 }
+// ELLHIP_OPT_APPLY_SYMM: the rank of the apply pass flush_pending would run on the matrix cores right now (k_apply_mfma<48> when
+// more are recorded than the depth, <24> at depth 24 where the option picks that kernel), 0 where it would pick another kernel or
+// the fused pass does not exist (shards: row0 != 0; the tile queue needs n % 64 == 0)
+int apply_symm_np(const ellhip_space* s) {
+    if (!s->apply_symm || s->sharded || s->variant != ELLHIP_SPACE_ELL || !s->apply_lower || !symv_ok(s) || !multi_mfma(s) ||
+        s->symm_ntiles == 0)
+        return 0;
+    if (s->npend > s->defer) return MAXPEND;
+    const int apply_kernel = s->apply_kernel < 0 ? (s->defer == 24 ? 2 : 1) : s->apply_kernel;
+    return (apply_kernel == 2 && s->defer == 24) ? 24 : 0;
+}
+
+// The apply pass a full set of recorded updates still owes, fused with the product pass of the group at `g_dev` (k_apply_symm_q:
+// one sweep over the lower triangle instead of k_apply_mfma's and k_symm_mfma_q's), then the slots are forgotten as after
+// flush_pending.  `owed` is cleared once the pass is issued.
+template <int SEG>
+void apply_symm_mfma_go(ellhip_space* s, const double* g_dev, int lv, int half, int np) {
+    double* gT = s->d_gT + (size_t)half * (size_t)s->n * MULTI_MAX;
+    double* rowp = s->d_rowpart_m + (size_t)half * MULTI_MAX * rowpart_elems(s);
+    double* colp = s->d_colpart_m + (size_t)half * MULTI_MAX * colpart_elems(s);
+    unsigned* queue = s->d_symm_queue + 32 * half;
+    const int nvw = lv > SMM_NV ? SMM_NV2 : SMM_NV;
+    hipLaunchKernelGGL(k_pack_grads, dim3((unsigned)((s->n * nvw + 255) / 256)), dim3(256), 0, s->stream, g_dev, s->n, lv, s->n, gT,
+                       queue, nvw);
+    const bool nt = s->sh_gemv.nt != 0;
+#define ELLHIP_APPLY_SYMM(...)                                                                                                      \
+    hipLaunchKernelGGL((__VA_ARGS__), dim3((unsigned)s->symm_wgs), dim3(256), 0, s->stream, s->d_Q, s->ld, s->n,                    \
+                       (const double*)s->d_pend, (const double*)s->d_cpend, (const double*)gT, lv, rowp, colp,                      \
+                       (long long)rowpart_elems(s), (long long)colpart_elems(s), (const DevState*)s->d_st,                         \
+                       (const SymmTile*)s->d_symm_tiles, s->symm_ntiles, queue)
+#define ELLHIP_APPLY_SYMM_NP(NPV)                                                                                                   \
+    if (nvw == SMM_NV) {                                                                                                            \
+        if (nt) ELLHIP_APPLY_SYMM(k_apply_symm_q<NPV, true, SEG, false>);                                                           \
+        else ELLHIP_APPLY_SYMM(k_apply_symm_q<NPV, false, SEG, false>);                                                             \
+    } else {                                                                                                                        \
+        if (nt) ELLHIP_APPLY_SYMM(k_apply_symm_q<NPV, true, SEG, true>);                                                            \
+        else ELLHIP_APPLY_SYMM(k_apply_symm_q<NPV, false, SEG, true>);                                                              \
+    }
+    if (np == MAXPEND) {
+        ELLHIP_APPLY_SYMM_NP(MAXPEND)
+    } else {
+        ELLHIP_APPLY_SYMM_NP(24)
+    }
+#undef ELLHIP_APPLY_SYMM_NP
+#undef ELLHIP_APPLY_SYMM
+}
+int apply_symm_go(ellhip_space* s, const double* g_dev, int lv, int half, int np, bool& owed) {
+    {
+        ProfScope ps(s, CLS_APPLY_GEMV);
+        if (s->symv_seg == SYMV_SEG) apply_symm_mfma_go<SYMV_SEG>(s, g_dev, lv, half, np);
+        else apply_symm_mfma_go<SYMV_SEG_SMALL>(s, g_dev, lv, half, np);
+        HIPCHK(hipGetLastError());
+    }
+    owed = false;
+    s->upper_stale = true;
+    s->dir ^= 1;
+    return pend_reset(s);
+}
+// an error return from a queue run leaves no apply pass owed
+struct OwedGuard {
+    ellhip_space* s;
+    bool& owed;
+    ~OwedGuard() {
+        if (!owed) return;
+        owed = false;
+        (void)flush_pending(s, nullptr, nullptr);
+    }
+};
+
 // How many of the `rem` cuts up to the next apply pass (or the end of the run) go into the next group, `cap` = what the handle's
 // lookahead and the kernels allow.  A matrix-core pass costs about the same for 4 gradients as for 16 (0.27 ms at n = 16384) and
 // 0.40-0.45 for 17-32 (two column tiles over the same block of Q), so: as many as fit; and where only the 16-wide pass is allowed
@@ -1802,6 +1899,11 @@ int queue_run_multi(ellhip_space* s, long long first, long long count) {
         if (rc) return rc;
     }
     SideGuard guard{s};
+    // ELLHIP_OPT_APPLY_SYMM: when a group fills the slots and another group follows inside this run, the apply pass stays owed
+    // and the next trip issues it fused with that group's products (k_apply_symm_q).  Not when that group ends the run: the
+    // run's last group keeps the separate passes (and the launch counts the suite pins for groups of 32, 16 | 8).
+    bool owed = false;
+    OwedGuard oguard{s, owed};
     int half = 0;                       // the half of the partial-sum sets the current group's products are in
     long long ahead_i = -1, ahead_g = 0;  // the group whose products are in flight on the second stream
     long long i = first;
@@ -1810,13 +1912,14 @@ int queue_run_multi(ellhip_space* s, long long first, long long count) {
         if (!(s->primed && s->primed_qindex == i)) {
             rc = ensure_committed(s);
             if (rc) return rc;
-            const long long room = (long long)qdepth - s->npend;  // cuts that can still be recorded before the apply pass
+            const long long room = (long long)qdepth - (owed ? 0 : s->npend);  // cuts that can still be recorded before the apply pass
             const long long cap = std::min<long long>(s->lookahead, multi_mfma(s) ? MULTI_MAX : MULTI_VALU_MAX);
             const long long rem = std::min(end - i, room);  // cuts up to the next apply pass or the end of the run
             g = group_size(s, cap, rem);
         }
         if (g <= 1 && !s->sharded) {  // a cut primed earlier, the last one before an apply pass, the last one of the run
             if (s->npend >= s->defer) {  // (the per-cut kernels hold `depth` recorded updates)
+                owed = false;
                 rc = flush_pending(s, nullptr, nullptr);
                 if (rc) return rc;
             }
@@ -1831,7 +1934,10 @@ int queue_run_multi(ellhip_space* s, long long first, long long count) {
             const long long cap = MULTI_MAX;
             rc = side_join(s);  // (this group's products, when they were issued ahead)
             if (rc) return rc;
-            if (!(ahead_i == i && ahead_g == g)) {  // this group's products are not in the sets yet
+            if (owed) {  // (nothing was issued ahead: the previous group filled the slots)
+                rc = apply_symm_go(s, qgrad(s, i), (int)g, half, apply_symm_np(s), owed);
+                if (rc) return rc;
+            } else if (!(ahead_i == i && ahead_g == g)) {  // this group's products are not in the sets yet
                 rc = symm_go(s, qgrad(s, i), (int)g, s->stream, half);
                 if (rc) return rc;
             }
@@ -1873,8 +1979,16 @@ int queue_run_multi(ellhip_space* s, long long first, long long count) {
             s->scalars_stale = true;
             s->shrink_pending = false;
             if (s->npend >= qdepth) {
-                rc = flush_pending(s, nullptr, nullptr);
-                if (rc) return rc;
+                const long long in = i + g;
+                long long gn = 0;  // the next group, sized as the loop head will size it once the slots are free
+                if (in < end && apply_symm_np(s) != 0)
+                    gn = group_size(s, std::min<long long>(s->lookahead, MULTI_MAX), std::min<long long>(end - in, qdepth));
+                if (gn >= 2 && in + gn < end) {
+                    owed = true;
+                } else {
+                    rc = flush_pending(s, nullptr, nullptr);
+                    if (rc) return rc;
+                }
             }
             if (ahead_i >= 0) half ^= 1;
             i += g;
@@ -2183,6 +2297,7 @@ int ellhip_clone(const ellhip_space* src_c, ellhip_space** out) {
     s->overlap = src->overlap;
     s->lookahead = src->lookahead;
     s->queue_depth = src->queue_depth;
+    s->apply_symm = src->apply_symm;
     s->resident = src->resident;
     s->shard_symmetric = src->shard_symmetric;
     s->upper_stale = src->upper_stale;
@@ -2490,7 +2605,8 @@ int option_ok(int key, long long v) {
     switch (key) {
         case ELLHIP_OPT_APPLY_KERNEL:
             return (v >= -1 && v <= 2) ? 0 : fail(ELLHIP_E_INVALID, "option value must be -1, 0, 1 or 2");
-        case ELLHIP_OPT_STAGE_DIRECT: return (v == 0 || v == 1) ? 0 : fail(ELLHIP_E_INVALID, "option value must be 0 or 1");
+        case ELLHIP_OPT_STAGE_DIRECT: case ELLHIP_OPT_APPLY_SYMM:
+            return (v == 0 || v == 1) ? 0 : fail(ELLHIP_E_INVALID, "option value must be 0 or 1");
         case ELLHIP_OPT_AUTO_DEFER: case ELLHIP_OPT_SYMV: case ELLHIP_OPT_APPLY_LOWER:
         case ELLHIP_OPT_FUSE_DOTS:
             return (v == 0 || v == 1) ? 0 : fail(ELLHIP_E_INVALID, "option value must be 0 or 1");
@@ -2527,6 +2643,7 @@ int ellhip_set_default_option(int key, int64_t value) {
         case ELLHIP_OPT_OVERLAP: g_defaults.overlap = (int)value; break;
         case ELLHIP_OPT_LOOKAHEAD: g_defaults.lookahead = (int)value; break;
         case ELLHIP_OPT_QUEUE_DEPTH: g_defaults.queue_depth = (int)value; break;
+        case ELLHIP_OPT_APPLY_SYMM: g_defaults.apply_symm = (int)value; break;
         case ELLHIP_OPT_STABLE_SOLVE: g_defaults.stable_solve = (int)value; break;
         case ELLHIP_OPT_STABLE_FACTOR: g_defaults.stable_factor = (int)value; break;
         case ELLHIP_OPT_PAD: g_defaults.pad = (int)value; break;
@@ -2551,6 +2668,7 @@ int ellhip_default_option(int key, int64_t* value) {
         case ELLHIP_OPT_OVERLAP: *value = g_defaults.overlap; break;
         case ELLHIP_OPT_LOOKAHEAD: *value = g_defaults.lookahead; break;
         case ELLHIP_OPT_QUEUE_DEPTH: *value = g_defaults.queue_depth; break;
+        case ELLHIP_OPT_APPLY_SYMM: *value = g_defaults.apply_symm; break;
         case ELLHIP_OPT_STABLE_SOLVE: *value = g_defaults.stable_solve; break;
         case ELLHIP_OPT_STABLE_FACTOR: *value = g_defaults.stable_factor; break;
         case ELLHIP_OPT_PAD: *value = g_defaults.pad; break;
@@ -2586,6 +2704,10 @@ int ellhip_set_option(ellhip_space* s, int key, int64_t value) {
         case ELLHIP_OPT_QUEUE_DEPTH:
             if (!ell) return fail(ELLHIP_E_INVALID, "this option exists on Ell only");
             s->queue_depth = (int)value;
+            return 0;
+        case ELLHIP_OPT_APPLY_SYMM:
+            if (!ell) return fail(ELLHIP_E_INVALID, "this option exists on Ell only");
+            s->apply_symm = (int)value;
             return 0;
         case ELLHIP_OPT_RESIDENT_FAULT:
             if (!ell) return fail(ELLHIP_E_INVALID, "this option exists on Ell only");
@@ -2638,6 +2760,7 @@ int ellhip_get_option(const ellhip_space* s, int key, int64_t* value) {
         case ELLHIP_OPT_OVERLAP: *value = s->overlap; break;
         case ELLHIP_OPT_LOOKAHEAD: *value = s->lookahead; break;
         case ELLHIP_OPT_QUEUE_DEPTH: *value = s->queue_depth; break;
+        case ELLHIP_OPT_APPLY_SYMM: *value = s->apply_symm; break;
         case ELLHIP_OPT_RESIDENT_FAULT: *value = s->rs_fault_at; break;
         case ELLHIP_OPT_RESIDENT_ABANDONED: *value = s->rs_abandoned; break;
         case ELLHIP_OPT_STABLE_SOLVE: *value = s->stable_solve; break;

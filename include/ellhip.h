@@ -262,6 +262,12 @@ int ellhip_set_shard_symmetric(ellhip_space *s, int flag);
  *                                                    stage is sized for it): half as many apply passes; on return fewer
  *                                                    than the handle's depth are left, as everywhere else.  0: never
  *                                                    more than the handle's depth
+ *   ELLHIP_OPT_APPLY_SYMM        0 / 1      1        Ell, ellhip_queue_run_fused with the matrix-core groups, unsharded: when
+ *                                                    the recorded updates fill the slots and a group that is not the run's
+ *                                                    last follows, their rank-24 / rank-48 apply pass (k_apply_mfma) and
+ *                                                    that group's product pass are ONE pass over the lower triangle
+ *                                                    (12 n^2 bytes instead of 16 n^2); profiled as apply_gemv.  Identical
+ *                                                    bits to 0 (two passes)
  *   ELLHIP_OPT_STABLE_SOLVE      0 .. 3     3        EllStable: 0 = one launch per 128-block (no in-launch waits),
  *                                                    1 = persistent solves, 2 = persistent + helper workgroups,
  *                                                    3 = 2 on the MIRRORED layout: the handle's private buffer holds the
@@ -306,6 +312,7 @@ int ellhip_set_shard_symmetric(ellhip_space *s, int flag);
 #define ELLHIP_OPT_STAGE_DIRECT 20      /* default only (0 / 1, default 1; per handle: read only): on a large-BAR system the host
                                            writes each gradient straight into (fine-grained) device memory instead of into a
                                            pinned buffer a kernel then pulls over PCIe */
+#define ELLHIP_OPT_APPLY_SYMM 21
 int ellhip_set_option(ellhip_space *s, int key, int64_t value);
 int ellhip_get_option(const ellhip_space *s, int key, int64_t *value);
 int ellhip_set_default_option(int key, int64_t value);
