@@ -1,6 +1,7 @@
 """Python mirror of the batched small-n engine (include/ellhip_batch.h): B independent `Ell` search spaces
 (src/ell.rs) of one dimension n <= 128 updated together, one workgroup per ellipsoid, bit-identical to the CPU
-arithmetic.  Cuts are arrays over the batch: `grads[B][n]`, `beta0[B]`, `beta1[B]` (NaN = None)."""
+arithmetic; `EllStableBatch` holds B `EllStable` spaces (src/ell_stable.rs) the same way.  Cuts are arrays over the
+batch: `grads[B][n]`, `beta0[B]`, `beta1[B]` (NaN = None)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -11,7 +12,10 @@ from . import capi
 from .ell import _f64, _p
 
 
-class EllBatch:
+class _Batch:
+    _create = ""        # C constructor of the variant
+    _from_space = ""    # C clone-of-one-handle constructor of the variant
+
     def __init__(self, kappa, mq, xc, *, diag=None, device: int = -1, _handle=None):
         self._lib = capi.load()
         if _handle is None:
@@ -23,14 +27,14 @@ class EllBatch:
             mq = None if mq is None else _f64(mq, B * n * n)
             diag = None if diag is None else _f64(diag, B * n)
             h = C.c_void_p()
-            capi.check(self._lib.ellhip_batch_create(C.byref(h), B, n, _p(kappa), _p(mq), _p(diag), _p(xc), device),
-                       "ellhip_batch_create")
+            capi.check(getattr(self._lib, self._create)(C.byref(h), B, n, _p(kappa), _p(mq), _p(diag), _p(xc), device),
+                       self._create)
             _handle = h
         self._h = _handle
         self.B = int(self._lib.ellhip_batch_size(self._h))
         self.n = int(self._lib.ellhip_batch_ndim(self._h))
 
-    # constructors, src/ell.rs:31-78 per ellipsoid
+    # constructors, src/ell.rs:31-78 / src/ell_stable.rs:18-35 per ellipsoid
     @classmethod
     def new_with_matrix(cls, kappa, mq, xc, **kw):
         return cls(kappa, mq, xc, **kw)
@@ -45,11 +49,18 @@ class EllBatch:
 
     @classmethod
     def from_space(cls, space, B: int):
-        """B clones of one `Ell` (BSearchAdaptor's clone-per-probe, src/cutting_plane.rs:410)."""
+        """B clones of one space of the batch's variant (BSearchAdaptor's clone-per-probe, src/cutting_plane.rs:410)."""
         lib = capi.load()
         h = C.c_void_p()
-        capi.check(lib.ellhip_batch_from_space(C.byref(h), space._h, int(B)), "ellhip_batch_from_space")
+        capi.check(getattr(lib, cls._from_space)(C.byref(h), space._h, int(B)), cls._from_space)
         return cls(None, None, None, _handle=h)
+
+    @property
+    def variant(self) -> int:
+        """capi.SPACE_ELL or capi.SPACE_ELL_STABLE"""
+        v = int(self._lib.ellhip_batch_variant(self._h))
+        capi.check(min(v, 0), "ellhip_batch_variant")
+        return v
 
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None
@@ -111,8 +122,21 @@ class EllBatch:
     def tsq(self):
         return self._get("ellhip_batch_get_tsq", (self.B,))
 
+    def set_use_parallel_cut(self, flag: bool):
+        capi.check(self._lib.ellhip_batch_set_use_parallel_cut(self._h, int(flag)))
+
+
+class EllBatch(_Batch):
+    """B `Ell` spaces."""
+    _create = "ellhip_batch_create"
+    _from_space = "ellhip_batch_from_space"
+
     def set_no_defer_trick(self, flag: bool):
         capi.check(self._lib.ellhip_batch_set_no_defer_trick(self._h, int(flag)))
 
-    def set_use_parallel_cut(self, flag: bool):
-        capi.check(self._lib.ellhip_batch_set_use_parallel_cut(self._h, int(flag)))
+
+class EllStableBatch(_Batch):
+    """B `EllStable` spaces: `mq` is each one's packed buffer (diagonal = D, strict upper = the factor, strict lower =
+    scratch), exactly as `EllStable.mq` and the oracle hold it."""
+    _create = "ellhip_batch_create_stable"
+    _from_space = "ellhip_batch_stable_from_space"

@@ -3,9 +3,11 @@
 #include "../../include/ellhip_batch.h"
 
 #include "batch_kernels.hpp"
+#include "batch_stable_kernels.hpp"
 
 struct ellhip_batch {
     int device = 0;
+    int variant = ELLHIP_SPACE_ELL;  // ELLHIP_SPACE_ELL: k_batch_update; ELLHIP_SPACE_ELL_STABLE: k_batch_update_stable
     long long B = 0;
     int n = 0;
     int T = 64;    // threads per workgroup
@@ -33,7 +35,32 @@ int batch_alloc(ellhip_batch* h) {
     return 0;
 }
 
+// EllStable (batch_stable_kernels.hpp): one wave per workgroup, one lane per ellipsoid; as many ellipsoids per workgroup as
+// fit in 40 KiB of LDS (four workgroups, one per SIMD, share a CU), at most 64 and at most BATCH_ST_GREGS * 64 gradient
+// entries per cut.  From n = 64 up one ellipsoid fills the workgroup (n = 128: 133 KiB, one per CU).
+int batch_shape_stable(ellhip_batch* h) {
+    h->T = BATCH_ST_T;
+    const size_t per_bytes = batch_stable_lds_doubles(h->n) * sizeof(double);
+    h->epw = (int)std::min<size_t>(64, std::max<size_t>(1, (40 * 1024) / per_bytes));
+    while (h->epw > 1 && h->epw * h->n > BATCH_ST_GREGS * BATCH_ST_T) h->epw -= 1;
+    h->lds_bytes = (size_t)h->epw * per_bytes;
+    if (h->lds_bytes > 160 * 1024) return fail(ELLHIP_E_INVALID, "batched engine: n too large for LDS");
+    constexpr int MAXDEV = 64;
+    static std::atomic<int> granted[MAXDEV];
+    const int dev = (h->device >= 0 && h->device < MAXDEV) ? h->device : -1;
+    if (dev < 0 || (int)h->lds_bytes > granted[dev].load()) {  // only ever raised, as in batch_shape
+        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_batch_update_stable),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_bytes));
+        if (dev >= 0) {
+            int seen = granted[dev].load();
+            while (seen < (int)h->lds_bytes && !granted[dev].compare_exchange_weak(seen, (int)h->lds_bytes)) {}
+        }
+    }
+    return 0;
+}
+
 int batch_shape(ellhip_batch* h) {
+    if (h->variant == ELLHIP_SPACE_ELL_STABLE) return batch_shape_stable(h);
     h->T = h->n <= 64 ? 256 : 128;
     if (g_defaults.batch_threads > 0) h->T = g_defaults.batch_threads;  // ELLHIP_OPT_BATCH_THREADS
     if (h->T != 64 && h->T != 128 && h->T != 256) return fail(ELLHIP_E_INVALID, "ELLHIP_OPT_BATCH_THREADS must be 64, 128 or 256");
@@ -80,6 +107,12 @@ int batch_launch(ellhip_batch* h, long long K, const int* kinds, const double* g
     P.no_defer_trick = h->no_defer_trick;
     const unsigned grid = (unsigned)((h->B + h->epw - 1) / h->epw);
     const EllCalcDev calc = EllCalcDev::make(h->n, h->use_parallel_cut);
+    if (h->variant == ELLHIP_SPACE_ELL_STABLE) {
+        hipLaunchKernelGGL(k_batch_update_stable, dim3(grid), dim3(BATCH_ST_T), h->lds_bytes, h->stream, P, h->d_Q, h->d_xc,
+                           h->d_kappa, h->d_tsq, kinds, grads, b0, hb1, b1, status, tsq_out, calc);
+        HIPCHK(hipGetLastError());
+        return 0;
+    }
 #define BATCH_GO(TT)                                                                                             \
     hipLaunchKernelGGL(k_batch_update<TT>, dim3(grid), dim3(TT), h->lds_bytes, h->stream, P, h->d_Q, h->d_xc,    \
                        h->d_kappa, h->d_tsq, kinds, grads, b0, hb1, b1, status, tsq_out, calc)
@@ -91,7 +124,7 @@ int batch_launch(ellhip_batch* h, long long K, const int* kinds, const double* g
     return 0;
 }
 
-int batch_new(ellhip_batch** out, long long B, long long n, int device) {
+int batch_new(ellhip_batch** out, long long B, long long n, int device, int variant) {
     if (!out) return fail(ELLHIP_E_INVALID, "out is NULL");
     *out = nullptr;
     if (B < 1 || n < 1 || n > BATCH_NMAX) return fail(ELLHIP_E_INVALID, "batched engine: need B >= 1 and 1 <= n <= 128");
@@ -103,6 +136,7 @@ int batch_new(ellhip_batch** out, long long B, long long n, int device) {
     ellhip_batch* h = new (std::nothrow) ellhip_batch();
     if (!h) return fail(ELLHIP_E_NOMEM, "host allocation failed");
     h->device = device;
+    h->variant = variant;
     h->B = B;
     h->n = (int)n;
     DeviceGuard guard(device);
@@ -116,14 +150,10 @@ int batch_new(ellhip_batch** out, long long B, long long n, int device) {
     return 0;
 }
 
-}  // namespace
-
-extern "C" {
-
-int ellhip_batch_create(ellhip_batch** out, int64_t B, int64_t n, const double* kappa, const double* mq,
-                        const double* diag, const double* xc, int device) {
+int batch_create(ellhip_batch** out, int64_t B, int64_t n, const double* kappa, const double* mq, const double* diag,
+                 const double* xc, int device, int variant) {
     ellhip_batch* h = nullptr;
-    int rc = batch_new(&h, B, n, device);
+    int rc = batch_new(&h, B, n, device, variant);
     if (rc) return rc;
     DeviceGuard guard(h->device);
     auto bail = [&](int code) {
@@ -163,20 +193,17 @@ int ellhip_batch_create(ellhip_batch** out, int64_t B, int64_t n, const double* 
     return 0;
 }
 
-int ellhip_batch_from_space(ellhip_batch** out, const ellhip_space* space_c, int64_t B) {
-    if (!space_c) return fail(ELLHIP_E_INVALID, "NULL handle");
-    ellhip_space* s = const_cast<ellhip_space*>(space_c);
-    if (s->variant != ELLHIP_SPACE_ELL || s->sharded)
-        return fail(ELLHIP_E_INVALID, "batched engine: clones of an unsharded Ell only");
+// B clones of one unsharded space: its buffer as ellhip_get_mq returns it, xc, kappa and tsq.
+int batch_clone_space(ellhip_batch** out, ellhip_space* s, int64_t B) {
     DeviceGuard guard(s->device);
-    int rc = make_q_current(s);  // recorded (deferred) shrinks belong to the matrix that is cloned
+    int rc = make_q_current(s);  // recorded (deferred) shrinks / EllStable's mirrored layout belong to the buffer that is cloned
     if (rc) return rc;
     rc = read_back(s);
     if (rc) return rc;
     ellhip_batch* h = nullptr;
-    rc = batch_new(&h, B, s->n, s->device);
+    rc = batch_new(&h, B, s->n, s->device, s->variant);
     if (rc) return rc;
-    h->no_defer_trick = s->no_defer_trick;
+    h->no_defer_trick = s->variant == ELLHIP_SPACE_ELL ? s->no_defer_trick : 0;
     h->use_parallel_cut = s->use_parallel_cut;
     const size_t n = (size_t)s->n;
     hipError_t e = hipSuccess;
@@ -196,6 +223,47 @@ int ellhip_batch_from_space(ellhip_batch** out, const ellhip_space* space_c, int
     }
     *out = h;
     return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ellhip_batch_create(ellhip_batch** out, int64_t B, int64_t n, const double* kappa, const double* mq,
+                        const double* diag, const double* xc, int device) {
+    return batch_create(out, B, n, kappa, mq, diag, xc, device, ELLHIP_SPACE_ELL);
+}
+
+// The constructors of EllStable (src/ell_stable.rs:18-35) build the same buffers as those of Ell: mq verbatim, diag(d) or
+// the identity.
+int ellhip_batch_create_stable(ellhip_batch** out, int64_t B, int64_t n, const double* kappa, const double* mq,
+                               const double* diag, const double* xc, int device) {
+    return batch_create(out, B, n, kappa, mq, diag, xc, device, ELLHIP_SPACE_ELL_STABLE);
+}
+
+int ellhip_batch_from_space(ellhip_batch** out, const ellhip_space* space_c, int64_t B) {
+    if (!space_c) return fail(ELLHIP_E_INVALID, "NULL handle");
+    ellhip_space* s = const_cast<ellhip_space*>(space_c);
+    if (s->variant != ELLHIP_SPACE_ELL || s->sharded)
+        return fail(ELLHIP_E_INVALID, "batched engine: clones of an unsharded Ell only");
+    return batch_clone_space(out, s, B);
+}
+
+int ellhip_batch_stable_from_space(ellhip_batch** out, const ellhip_space* space_c, int64_t B) {
+    if (ellhip_device_count() <= 0) return fail(ELLHIP_E_NODEVICE, "no HIP device: the batched engine has no CPU path");
+    if (!space_c) return fail(ELLHIP_E_INVALID, "NULL handle");
+    ellhip_space* s = const_cast<ellhip_space*>(space_c);
+    if (s->variant != ELLHIP_SPACE_ELL_STABLE || s->sharded)
+        return fail(ELLHIP_E_INVALID, "batched engine: clones of an unsharded EllStable only");
+    return batch_clone_space(out, s, B);
+}
+
+int ellhip_batch_variant(const ellhip_batch* h) {
+    if (!h) {
+        if (ellhip_device_count() <= 0) return fail(ELLHIP_E_NODEVICE, "no HIP device: the batched engine has no CPU path");
+        return fail(ELLHIP_E_INVALID, "NULL handle");
+    }
+    return h->variant;
 }
 
 void ellhip_batch_destroy(ellhip_batch* h) {
@@ -305,6 +373,7 @@ int64_t ellhip_batch_ndim(const ellhip_batch* h) { return h ? h->n : 0; }
 
 int ellhip_batch_set_no_defer_trick(ellhip_batch* h, int flag) {
     if (!h) return fail(ELLHIP_E_INVALID, "NULL handle");
+    if (h->variant != ELLHIP_SPACE_ELL) return fail(ELLHIP_E_INVALID, "no_defer_trick exists on Ell only");
     h->no_defer_trick = flag ? 1 : 0;
     return 0;
 }

@@ -2,7 +2,7 @@
 // (include/ellhip_batch.h).  The C++ counterpart of a `Vec<Ell>` whose elements are updated together:
 // `update_bias_cut(cuts)` is `for b in 0..B { space[b].update_bias_cut(&cuts[b]) }` in one launch, bit-identical to
 // the CPU arithmetic.  `from_space` makes B clones of one EllHip (BSearchAdaptor's clone per probe,
-// src/cutting_plane.rs:410).
+// src/cutting_plane.rs:410).  EllStableBatchHip is the same for a `Vec<EllStable>` (clones of one EllStableHip).
 #pragma once
 
 #include <cstdint>
@@ -13,33 +13,37 @@
 
 namespace ellhip {
 
-class EllBatchHip {
+template <int VARIANT>
+class BatchHip {
   public:
-    // Ell::new_with_scalar(val[b], xc[b]) for every b (src/ell.rs:71-73)
-    static EllBatchHip new_with_scalar(const Arr& val, const std::vector<Arr>& xc, int device = -1) {
-        return EllBatchHip(&val, nullptr, nullptr, xc, device);
+    // Ell::new_with_scalar(val[b], xc[b]) for every b (src/ell.rs:71-73; EllStable: src/ell_stable.rs:33-35)
+    static BatchHip new_with_scalar(const Arr& val, const std::vector<Arr>& xc, int device = -1) {
+        return BatchHip(&val, nullptr, nullptr, xc, device);
     }
-    // Ell::new(diag[b], xc[b]) (:55-57)
-    static EllBatchHip make(const std::vector<Arr>& diag, const std::vector<Arr>& xc, int device = -1) {
-        return EllBatchHip(nullptr, nullptr, &diag, xc, device);
+    // Ell::new(diag[b], xc[b]) (:55-57; EllStable: :29-31)
+    static BatchHip make(const std::vector<Arr>& diag, const std::vector<Arr>& xc, int device = -1) {
+        return BatchHip(nullptr, nullptr, &diag, xc, device);
     }
-    // Ell::new_with_matrix(kappa[b], mq[b], xc[b]) (:31-41); mq[b] is n*n row-major
-    static EllBatchHip new_with_matrix(const Arr& kappa, const std::vector<Arr>& mq, const std::vector<Arr>& xc,
-                                       int device = -1) {
-        return EllBatchHip(&kappa, &mq, nullptr, xc, device);
+    // Ell::new_with_matrix(kappa[b], mq[b], xc[b]) (:31-41; EllStable: :18-27); mq[b] is n*n row-major
+    static BatchHip new_with_matrix(const Arr& kappa, const std::vector<Arr>& mq, const std::vector<Arr>& xc,
+                                    int device = -1) {
+        return BatchHip(&kappa, &mq, nullptr, xc, device);
     }
-    template <int VARIANT>
-    static EllBatchHip from_space(SpaceHip<VARIANT>& space, std::size_t B) {
-        EllBatchHip r;
-        check(ellhip_batch_from_space(&r.h_, space.handle(), (int64_t)B), "ellhip_batch_from_space");
+    template <int SPACE>
+    static BatchHip from_space(SpaceHip<SPACE>& space, std::size_t B) {
+        BatchHip r;
+        if (VARIANT == ELLHIP_SPACE_ELL_STABLE)
+            check(ellhip_batch_stable_from_space(&r.h_, space.handle(), (int64_t)B), "ellhip_batch_stable_from_space");
+        else
+            check(ellhip_batch_from_space(&r.h_, space.handle(), (int64_t)B), "ellhip_batch_from_space");
         r.B_ = B;
         r.n_ = space.ndim();
         return r;
     }
-    EllBatchHip(const EllBatchHip&) = delete;
-    EllBatchHip& operator=(const EllBatchHip&) = delete;
-    EllBatchHip(EllBatchHip&& o) noexcept : h_(o.h_), B_(o.B_), n_(o.n_) { o.h_ = nullptr; }
-    ~EllBatchHip() { ellhip_batch_destroy(h_); }
+    BatchHip(const BatchHip&) = delete;
+    BatchHip& operator=(const BatchHip&) = delete;
+    BatchHip(BatchHip&& o) noexcept : h_(o.h_), B_(o.B_), n_(o.n_) { o.h_ = nullptr; }
+    ~BatchHip() { ellhip_batch_destroy(h_); }
 
     std::size_t size() const { return B_; }
     std::size_t ndim() const { return n_; }
@@ -78,22 +82,28 @@ class EllBatchHip {
         check(ellhip_batch_get_tsq(h_, t.data()), "ellhip_batch_get_tsq");
         return t;
     }
-    void set_no_defer_trick(bool f) { check(ellhip_batch_set_no_defer_trick(h_, f ? 1 : 0), "set_no_defer_trick"); }
+    void set_no_defer_trick(bool f) {
+        static_assert(VARIANT == ELLHIP_SPACE_ELL, "no_defer_trick exists on Ell only");
+        check(ellhip_batch_set_no_defer_trick(h_, f ? 1 : 0), "set_no_defer_trick");
+    }
+    void set_use_parallel_cut(bool f) { check(ellhip_batch_set_use_parallel_cut(h_, f ? 1 : 0), "set_use_parallel_cut"); }
     ellhip_batch* handle() { return h_; }
 
   private:
-    EllBatchHip() = default;
-    EllBatchHip(const Arr* kappa, const std::vector<Arr>* mq, const std::vector<Arr>* diag, const std::vector<Arr>& xc,
-                int device)
+    BatchHip() = default;
+    BatchHip(const Arr* kappa, const std::vector<Arr>* mq, const std::vector<Arr>* diag, const std::vector<Arr>& xc,
+             int device)
         : B_(xc.size()), n_(xc.empty() ? 0 : xc[0].size()) {
         if (kappa && kappa->size() != B_) throw Error(ELLHIP_E_INVALID, "kappa must have B entries");
         const Arr fx = flatten(xc, n_);
         Arr fm, fd;
         if (mq) fm = flatten(*mq, n_ * n_);
         if (diag) fd = flatten(*diag, n_);
-        check(ellhip_batch_create(&h_, (int64_t)B_, (int64_t)n_, kappa ? kappa->data() : nullptr,
-                                  mq ? fm.data() : nullptr, diag ? fd.data() : nullptr, fx.data(), device),
-              "ellhip_batch_create");
+        const bool stable = VARIANT == ELLHIP_SPACE_ELL_STABLE;
+        check((stable ? ellhip_batch_create_stable : ellhip_batch_create)(
+                  &h_, (int64_t)B_, (int64_t)n_, kappa ? kappa->data() : nullptr, mq ? fm.data() : nullptr,
+                  diag ? fd.data() : nullptr, fx.data(), device),
+              stable ? "ellhip_batch_create_stable" : "ellhip_batch_create");
     }
     Arr flatten(const std::vector<Arr>& v, std::size_t each) const {
         if (v.size() != B_) throw Error(ELLHIP_E_INVALID, "need one entry per ellipsoid");
@@ -135,5 +145,9 @@ class EllBatchHip {
     ellhip_batch* h_ = nullptr;
     std::size_t B_ = 0, n_ = 0;
 };
+
+// a `Vec<Ell>` / a `Vec<EllStable>` behind one handle
+using EllBatchHip = BatchHip<ELLHIP_SPACE_ELL>;
+using EllStableBatchHip = BatchHip<ELLHIP_SPACE_ELL_STABLE>;
 
 }  // namespace ellhip

@@ -9,8 +9,13 @@
  * `Vec<Ell>` behind this handle and calls ellhip_batch_update where it would loop over
  * `space[b].update_bias_cut(&cut[b])`.
  *
+ * The same handle holds B `EllStable` spaces (src/ell_stable.rs:9-15) instead when it is made by
+ * ellhip_batch_create_stable or ellhip_batch_stable_from_space: each one's packed n x n buffer (diagonal = D, strict
+ * upper triangle = the factor, strict lower triangle = scratch), one lane per ellipsoid.
+ *
  * Every step follows the reference's statement order (row-wise left folds, rank-1 over j <= i with the mirror
- * store), so the results are bit-identical to the CPU arithmetic, not merely within 1e-10.
+ * store; EllStable's solves and factor update as in EllStable::update_core), so the results are bit-identical to
+ * the CPU arithmetic, not merely within 1e-10.
  * Same conventions as ellhip.h: host buffers owned by the caller unless the name ends in _dev, 0 = ok,
  * negative = ELLHIP_E_*, no CPU fallback.
  */
@@ -34,6 +39,16 @@ int ellhip_batch_create(ellhip_batch **out, int64_t B, int64_t n, const double *
                         const double *diag, const double *xc, int device);
 /* B clones of one unsharded Ell handle (`self.space.clone()` per probe, src/cutting_plane.rs:410). */
 int ellhip_batch_from_space(ellhip_batch **out, const ellhip_space *space, int64_t B);
+/* B EllStable ellipsoids of dimension n, with the conventions of ellhip_batch_create: mq B*n*n packed buffers taken
+ * verbatim (EllStable::new_with_matrix, src/ell_stable.rs:18-27; the strict lower triangle is scratch and may hold
+ * anything), or NULL with diag: B*n (EllStable::new, :29-31), or both NULL = identity (new_with_scalar, :33-35). */
+int ellhip_batch_create_stable(ellhip_batch **out, int64_t B, int64_t n, const double *kappa, const double *mq,
+                               const double *diag, const double *xc, int device);
+/* B clones of one unsharded EllStable handle, whatever its solve form or layout: each clone's buffer is what
+ * ellhip_get_mq returns at this moment, with the handle's xc, kappa and tsq.  Ell handles are refused. */
+int ellhip_batch_stable_from_space(ellhip_batch **out, const ellhip_space *space, int64_t B);
+/* ELLHIP_SPACE_ELL or ELLHIP_SPACE_ELL_STABLE */
+int ellhip_batch_variant(const ellhip_batch *h);
 void ellhip_batch_destroy(ellhip_batch *h);
 
 /* K cuts for each ellipsoid, applied in order k = 0..K-1, exactly as K successive calls of
@@ -52,7 +67,8 @@ int ellhip_batch_update_dev(ellhip_batch *h, int64_t K, const int32_t *kinds_dev
 int ellhip_batch_synchronize(ellhip_batch *h);
 void *ellhip_batch_stream(ellhip_batch *h); /* hipStream_t the handle issues on */
 
-/* state of all ellipsoids: xc [B][n], mq [B][n][n], kappa [B], tsq [B] */
+/* state of all ellipsoids: xc [B][n], mq [B][n][n] (EllStable: the packed buffers, scratch triangle included),
+ * kappa [B], tsq [B] */
 int ellhip_batch_get_xc(ellhip_batch *h, double *out);
 int ellhip_batch_set_xc(ellhip_batch *h, const double *xc);
 int ellhip_batch_get_mq(ellhip_batch *h, double *out);
@@ -60,7 +76,7 @@ int ellhip_batch_get_kappa(ellhip_batch *h, double *out);
 int ellhip_batch_get_tsq(ellhip_batch *h, double *out);
 int64_t ellhip_batch_size(const ellhip_batch *h);
 int64_t ellhip_batch_ndim(const ellhip_batch *h);
-int ellhip_batch_set_no_defer_trick(ellhip_batch *h, int flag);
+int ellhip_batch_set_no_defer_trick(ellhip_batch *h, int flag); /* Ell only: ELLHIP_E_INVALID on EllStable */
 int ellhip_batch_set_use_parallel_cut(ellhip_batch *h, int flag);
 
 #ifdef __cplusplus
