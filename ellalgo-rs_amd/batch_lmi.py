@@ -1,0 +1,94 @@
+"""Python mirror of the batched device-resident LMI cutting-plane loop (include/ellhip_batch_lmi.h): B independent
+problems `min c'x  s.t.  B_j - sum_k x_k F_jk > 0` (or, without mat_b, `sum_k x_k F_jk > 0`), each with its own
+round-robin oracle (tests/lmi_tests.rs:142-171 generalised to J blocks) and its own ellipsoid of an `EllBatch`, solved by
+one kernel per chunk of iterations.  Bit-identical to the CPU arithmetic."""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import capi
+from .ell import _f64, _p
+
+
+class BatchLmiProblem:
+    def __init__(self, mat_f, mat_b=None, c=None, *, device: int = -1):
+        """mat_f: a list of J arrays [B][n][m_j][m_j]; mat_b: a list of J arrays [B][m_j][m_j] or None (LMI0 form);
+        c: [B][n] or None (feasibility problem)."""
+        self._lib = capi.load()
+        mat_f = [np.ascontiguousarray(f, dtype=np.float64) for f in mat_f]
+        if not mat_f or any(f.ndim != 4 or f.shape[2] != f.shape[3] for f in mat_f):
+            raise ValueError("mat_f must be a list of [B][n][m][m] arrays")
+        B, n = mat_f[0].shape[:2]
+        if any(f.shape[:2] != (B, n) for f in mat_f):
+            raise ValueError("every block needs the same B and n")
+        m = np.array([f.shape[2] for f in mat_f], dtype=np.int64)
+        flat_f = np.concatenate([f.ravel() for f in mat_f])
+        flat_b = None
+        if mat_b is not None:
+            mat_b = [np.ascontiguousarray(b, dtype=np.float64) for b in mat_b]
+            if len(mat_b) != len(mat_f) or any(b.shape != (B, mj, mj) for b, mj in zip(mat_b, m)):
+                raise ValueError("mat_b must be a list of [B][m][m] arrays, one per block")
+            flat_b = np.concatenate([b.ravel() for b in mat_b])
+        c = None if c is None else _f64(c, B * n)
+        h = C.c_void_p()
+        capi.check(self._lib.ellhip_batch_lmi_create(C.byref(h), B, n, len(mat_f), _p(m), _p(flat_f), _p(flat_b), _p(c),
+                                                     device), "ellhip_batch_lmi_create")
+        self._h = h
+        self.B, self.n, self.J = int(B), int(n), len(mat_f)
+        self.has_c = c is not None
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            self._lib.ellhip_batch_lmi_destroy(h)
+
+    @property
+    def idx(self):
+        out = np.empty(self.B, dtype=np.int32)
+        capi.check(self._lib.ellhip_batch_lmi_get_idx(self._h, _p(out)), "ellhip_batch_lmi_get_idx")
+        return out
+
+    @idx.setter
+    def idx(self, value):
+        v = None if value is None else np.ascontiguousarray(np.broadcast_to(np.asarray(value, dtype=np.int32), (self.B,)))
+        capi.check(self._lib.ellhip_batch_lmi_set_idx(self._h, _p(v)), "ellhip_batch_lmi_set_idx")
+
+    def set_chunk(self, iters: int):
+        capi.check(self._lib.ellhip_batch_lmi_set_chunk(self._h, int(iters)), "ellhip_batch_lmi_set_chunk")
+
+    def assess_optim(self, x, gamma):
+        """One oracle call per problem.  Returns (grad [B][n], beta [B], station [B], gamma [B]); station J = objective
+        cut, J + 1 = shrunk."""
+        x = _f64(x, self.B * self.n)
+        gamma = np.array(np.broadcast_to(np.asarray(gamma, dtype=np.float64), (self.B,)))
+        grad = np.zeros((self.B, self.n))
+        beta = np.empty(self.B)
+        station = np.empty(self.B, dtype=np.int32)
+        capi.check(self._lib.ellhip_batch_lmi_assess_optim(self._h, _p(x), _p(gamma), _p(grad), _p(beta), _p(station)),
+                   "ellhip_batch_lmi_assess_optim")
+        return grad, beta, station, gamma
+
+    def optim(self, spaces, gamma, max_iters: int, tol: float):
+        """cutting_plane_optim per problem on `spaces` (an EllBatch).  Returns (x_best [B][n] with NaN rows where there
+        is none, has_best [B], niter [B], gamma [B], status [B])."""
+        gamma = np.array(np.broadcast_to(np.asarray(gamma, dtype=np.float64), (self.B,)))
+        x_best = np.full((self.B, self.n), np.nan)
+        has = np.empty(self.B, dtype=np.int32)
+        niter = np.empty(self.B, dtype=np.int64)
+        status = np.empty(self.B, dtype=np.int32)
+        capi.check(self._lib.ellhip_batch_lmi_optim(spaces._h, self._h, _p(gamma), int(max_iters), float(tol), _p(x_best),
+                                                    _p(has), _p(niter), _p(status)), "ellhip_batch_lmi_optim")
+        return x_best, has, niter, gamma, status
+
+    def feas(self, spaces, max_iters: int, tol: float):
+        """cutting_plane_feas per problem.  Returns (x [B][n] with NaN rows where infeasible, feasible [B], niter [B],
+        status [B])."""
+        x = np.full((self.B, self.n), np.nan)
+        ok = np.empty(self.B, dtype=np.int32)
+        niter = np.empty(self.B, dtype=np.int64)
+        status = np.empty(self.B, dtype=np.int32)
+        capi.check(self._lib.ellhip_batch_lmi_feas(spaces._h, self._h, int(max_iters), float(tol), _p(x), _p(ok), _p(niter),
+                                                   _p(status)), "ellhip_batch_lmi_feas")
+        return x, ok, niter, status

@@ -63,6 +63,12 @@ SVM_EXPORTS = [
     "ellhip_svm_optim",
 ]
 
+# every symbol include/ellhip_batch_lmi.h declares (kept apart from EXPORTS, like SVM_EXPORTS)
+BATCH_LMI_EXPORTS = [
+    "ellhip_batch_lmi_create", "ellhip_batch_lmi_destroy", "ellhip_batch_lmi_assess_optim", "ellhip_batch_lmi_get_idx",
+    "ellhip_batch_lmi_set_idx", "ellhip_batch_lmi_optim", "ellhip_batch_lmi_feas", "ellhip_batch_lmi_set_chunk",
+]
+
 
 class EllHipError(RuntimeError):
     pass
@@ -263,8 +269,17 @@ def load():
         "ellhip_svm_margins": (i32, [vp, vp, vp]),
         "ellhip_svm_last": (i32, [vp, C.POINTER(i64), C.POINTER(dbl)]),
         "ellhip_svm_optim": (i32, [vp, vp, C.POINTER(dbl), i64, dbl, vp, C.POINTER(i32), C.POINTER(i64)]),
+        # include/ellhip_batch_lmi.h
+        "ellhip_batch_lmi_create": (i32, [C.POINTER(vp), i64, i64, i64, vp, vp, vp, vp, i32]),
+        "ellhip_batch_lmi_destroy": (None, [vp]),
+        "ellhip_batch_lmi_assess_optim": (i32, [vp, vp, vp, vp, vp, vp]),
+        "ellhip_batch_lmi_get_idx": (i32, [vp, vp]),
+        "ellhip_batch_lmi_set_idx": (i32, [vp, vp]),
+        "ellhip_batch_lmi_optim": (i32, [vp, vp, vp, i64, dbl, vp, vp, vp, vp]),
+        "ellhip_batch_lmi_feas": (i32, [vp, vp, i64, dbl, vp, vp, vp, vp]),
+        "ellhip_batch_lmi_set_chunk": (i32, [vp, i64]),
     }
-    for name in EXPORTS + SVM_EXPORTS:
+    for name in EXPORTS + SVM_EXPORTS + BATCH_LMI_EXPORTS:
         fn = getattr(L, name)  # AttributeError if the library does not export it
         fn.restype, fn.argtypes = sig[name]
     _lib = L

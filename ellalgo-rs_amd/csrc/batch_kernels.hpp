@@ -67,6 +67,74 @@ __device__ __forceinline__ void batch_copy(double* __restrict__ sm, double* __re
     }
 }
 
+// One cut of Ell::update_core (src/ell.rs:97-137) for the workgroup's ellipsoids, out of LDS: thread (e, i) owns row i of
+// local ellipsoid e (q, g, gt, sc are that ellipsoid's LDS blocks, xci its xc[i]); `scalar_lane` t of wave 0 runs the scalar
+// stage for local ellipsoid t (g_s, gt_s, sc_s; kind_k, b0_k, hb1_k, b1_k: that ellipsoid's cut) and hands its status and
+// tsq to `emit`.  The caller has stored g and synchronised; the function ends with a barrier.  Shared by k_batch_update
+// and k_batch_lmi_loop (batch_lmi_kernels.hpp), so both apply a cut with the same instructions.
+template <class Emit>
+__device__ __forceinline__ void batch_cut_apply(const BatchParams& P, const EllCalcDev& calc, const bool active, const int i,
+                                                double* q, const double* g, double* gt, double* sc, double& xci,
+                                                const bool scalar_lane, const double* g_s, const double* gt_s, double* sc_s,
+                                                const int kind_k, const double b0_k, const int hb1_k, const double b1_k,
+                                                Emit emit) {
+    const int n = P.n, pitch = P.pitch;
+    if (active) {  // gt = Q g                                            src/ell.rs:102
+        double acc = 0.0;
+        const double* row = q + (size_t)i * pitch;
+#pragma unroll 8
+        for (int j = 0; j < n; ++j) acc += row[j] * g[j];  // loads run ahead, the adds stay in order
+        gt[i] = acc;
+    }
+    __syncthreads();
+    if (scalar_lane) {
+        double omega = 0.0;  //                                           :103
+#pragma unroll 8
+        for (int j = 0; j < n; ++j) omega += g_s[j] * gt_s[j];
+        const double kap = sc_s[4];
+        const double t = kap * omega;  //                                 :105
+        Coef cf;
+        const int st = calc.dispatch(kind_k, b0_k, hb1_k, b1_k, t, cf);  // :106
+        sc_s[5] = t;
+        sc_s[3] = (double)st;
+        if (st == ST_SUCCESS) {
+            sc_s[0] = cf.rho / omega;    //                               :112
+            sc_s[1] = cf.sigma / omega;  //                               :117
+            const double knew = kap * cf.delta;  //                       :130
+            if (P.no_defer_trick) {      //                               :132-135
+                sc_s[2] = knew;
+                sc_s[4] = 1.0;
+            } else {
+                sc_s[2] = 1.0;
+                sc_s[4] = knew;
+            }
+        }
+        emit(st, t);
+    }
+    __syncthreads();
+    const bool ok = active && sc[3] == (double)ST_SUCCESS;
+    if (ok) {
+        xci = xci - sc[0] * gt[i];  //                                    :113-115
+        const double r = sc[1] * gt[i];
+        double* row = q + (size_t)i * pitch;
+#pragma unroll 4
+        for (int j = 0; j <= i; ++j) {  //                                :119-128
+            const double v = row[j] - r * gt[j];
+            row[j] = v;
+            q[(size_t)j * pitch + i] = v;  // mirror store; nobody reads the upper triangle in this phase
+        }
+    }
+    if (P.no_defer_trick) {
+        __syncthreads();
+        if (ok) {
+            const double s = sc[2];
+            double* row = q + (size_t)i * pitch;
+            for (int j = 0; j < n; ++j) row[j] = row[j] * s;
+        }
+    }
+    __syncthreads();
+}
+
 // Cut k of ellipsoid b: kinds / beta arrays are [K][B], grads [K][B][n]; status / tsq outputs [K][B].
 template <int T>
 __global__ __launch_bounds__(T) void k_batch_update(BatchParams P, double* __restrict__ Q, double* __restrict__ xc,
@@ -133,62 +201,12 @@ __global__ __launch_bounds__(T) void k_batch_update(BatchParams P, double* __res
                 b1_next = beta1[nxt];
             }
         }
-        if (active) {  // gt = Q g                                            src/ell.rs:102
-            double acc = 0.0;
-            const double* row = q + (size_t)i * pitch;
-#pragma unroll 8
-            for (int j = 0; j < n; ++j) acc += row[j] * g[j];  // loads run ahead, the adds stay in order
-            gt[i] = acc;
-        }
-        __syncthreads();
-        if (scalar_lane) {
-            const long long cut_s = (long long)k * P.B + bs;
-            double omega = 0.0;  //                                           :103
-#pragma unroll 8
-            for (int j = 0; j < n; ++j) omega += g_s[j] * gt_s[j];
-            const double kap = sc_s[4];
-            const double t = kap * omega;  //                                 :105
-            Coef cf;
-            const int st = calc.dispatch(kind_k, b0_k, hb1_k, b1_k, t, cf);  // :106
-            sc_s[5] = t;
-            sc_s[3] = (double)st;
-            if (st == ST_SUCCESS) {
-                sc_s[0] = cf.rho / omega;    //                               :112
-                sc_s[1] = cf.sigma / omega;  //                               :117
-                const double knew = kap * cf.delta;  //                       :130
-                if (P.no_defer_trick) {      //                               :132-135
-                    sc_s[2] = knew;
-                    sc_s[4] = 1.0;
-                } else {
-                    sc_s[2] = 1.0;
-                    sc_s[4] = knew;
-                }
-            }
-            status_out[cut_s] = st;
-            if (tsq_out) tsq_out[cut_s] = t;
-        }
-        __syncthreads();
-        const bool ok = active && sc[3] == (double)ST_SUCCESS;
-        if (ok) {
-            xci = xci - sc[0] * gt[i];  //                                    :113-115
-            const double r = sc[1] * gt[i];
-            double* row = q + (size_t)i * pitch;
-#pragma unroll 4
-            for (int j = 0; j <= i; ++j) {  //                                :119-128
-                const double v = row[j] - r * gt[j];
-                row[j] = v;
-                q[(size_t)j * pitch + i] = v;  // mirror store; nobody reads the upper triangle in this phase
-            }
-        }
-        if (P.no_defer_trick) {
-            __syncthreads();
-            if (ok) {
-                const double s = sc[2];
-                double* row = q + (size_t)i * pitch;
-                for (int j = 0; j < n; ++j) row[j] = row[j] * s;
-            }
-        }
-        __syncthreads();
+        batch_cut_apply(P, calc, active, i, q, g, gt, sc, xci, scalar_lane, g_s, gt_s, sc_s, kind_k, b0_k, hb1_k, b1_k,
+                        [&](int st, double t) {
+                            const long long cut_s = (long long)k * P.B + bs;
+                            status_out[cut_s] = st;
+                            if (tsq_out) tsq_out[cut_s] = t;
+                        });
     }
 
     // ---- LDS -> Q, xc, kappa, tsq

@@ -2991,3 +2991,4 @@ int ellhip_profile_read(ellhip_space* s, double* ms_out, int64_t* count_out) {
 #include "lmi_capi.inc.hpp"
 #include "sharded_capi.inc.hpp"
 #include "svm_capi.inc.hpp"
+#include "batch_lmi_capi.inc.hpp"
