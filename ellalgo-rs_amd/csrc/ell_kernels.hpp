@@ -1090,6 +1090,77 @@ __global__ __launch_bounds__(256) void k_pack_grads(const double* __restrict__ g
     gT[i] = v < lv ? g[(long long)v * g_stride + c] : 0.0;
 }
 
+// ELLHIP_OPT_PACKED_OPERANDS: the operands the product passes fetch per 64 x 16 block, laid out so that a lane moves 16 bytes
+// per instruction (on a SIMD that executes f64 MFMAs a vector-memory instruction costs the matrix pipe its ~70 cycles whatever
+// its width).  Every MFMA receives the operands it received before, in the same order: only the address they come from -- and,
+// for the column sums, the tile slot a vector sits in, which does not enter its arithmetic -- changes.
+//   gP[((beta NVT + t) 2 + kb2) 64 + lane][e] = g_v[16 beta + 4 (2 kb2 + e) + (lane >> 4)],  v = pk_vec(t, lane & 15):
+//       the gc registers of block beta are 2 NVT contiguous 1 KiB loads; the strip's A operands (gr / sgr) read the same array;
+//   pendP[(cblk KS / 2 + s2) 64 + lane][e] = pend[4 (2 s2 + e) + (lane >> 4)][16 cblk + (lane & 15)]:
+//       the bv registers of the fused pass, KS / 2 loads;
+//   vector 2 p + e sits at slot (p & 3) + 8 ((p & 7) >> 2) + 4 e of tile p >> 3, so that a lane's accumulator elements i, i + 1
+//       (i even) are the column sums of vectors 2 p, 2 p + 1: one 16-byte store into colpart2[p][I][c][2] (k_group_reduce_p).
+// pk_vec: the vector at slot `slot` of tile t.
+__device__ __host__ __forceinline__ int pk_vec(int t, int slot) {
+    return 16 * t + 8 * (slot >> 3) + 2 * (slot & 3) + ((slot >> 2) & 1);
+}
+
+// The packed sibling of k_pack_grads (it rewinds the tile queue as well).  Workgroups [0, n nvt / 32) write gP, one 16-byte
+// pair per thread; the ks2 n / 64 workgroups after them write pendP (ks2 = KS / 2 of the fused pass that follows, 0: none).
+// n % 64 == 0.
+__global__ __launch_bounds__(256) void k_pack_operands(const double* __restrict__ g, long long g_stride, int lv, long long n,
+                                                       double* __restrict__ gP, unsigned* __restrict__ queue, int nvt,
+                                                       const double* __restrict__ pend, double* __restrict__ pendP, int ks2) {
+    const long long nbg = n * nvt / 32;
+    if ((long long)blockIdx.x < nbg) {
+        const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+        if (idx == 0 && queue) *queue = 0u;
+        const long long beta = idx / (nvt * 128);
+        const int rem = (int)(idx % (nvt * 128));
+        const int t = rem >> 7, kb2 = (rem >> 6) & 1, lane = rem & 63;
+        const int v = pk_vec(t, lane & 15);
+        const long long row = 16 * beta + 8 * kb2 + (lane >> 4);
+        double2_t o = {0.0, 0.0};
+        if (v < lv) o = double2_t{g[(long long)v * g_stride + row], g[(long long)v * g_stride + row + 4]};
+        reinterpret_cast<double2_t*>(gP)[idx] = o;
+        return;
+    }
+    const long long idx = ((long long)blockIdx.x - nbg) * 256 + threadIdx.x;
+    if (idx >= (n / 16) * ks2 * 64) return;
+    const long long cblk = idx / (ks2 * 64);
+    const int s2 = (int)((idx >> 6) % ks2), lane = (int)(idx & 63);
+    const long long k0 = 8 * s2 + (lane >> 4), col = 16 * cblk + (lane & 15);
+    reinterpret_cast<double2_t*>(pendP)[idx] = double2_t{pend[k0 * n + col], pend[(k0 + 4) * n + col]};
+}
+
+// the packed forms' operand fetches (gP as above; NVT = 16-wide column tiles of the pass)
+template <int NVT>
+__device__ __forceinline__ void pk_load_gc(const double* __restrict__ gP, long long cb, int t, int lane, double (&gc)[4]) {
+    const double2_t* p = reinterpret_cast<const double2_t*>(gP) + (((cb >> 4) * NVT + t) * 2) * 64 + lane;
+    const double2_t a = p[0], b = p[64];
+    gc[0] = a.x, gc[1] = a.y, gc[2] = b.x, gc[3] = b.y;
+}
+// the gT rows of the strip at r0 into sgr[row][16 t + slot], from gP
+template <int NVT, int PITCH>
+__device__ __forceinline__ void pk_stage_sgr(const double* __restrict__ gP, long long r0, double (*sgr)[PITCH]) {
+    const double2_t* p = reinterpret_cast<const double2_t*>(gP) + (r0 >> 4) * (NVT * 128);
+    for (int k = threadIdx.x; k < 4 * NVT * 128; k += 256) {
+        const double2_t v = p[k];
+        const int blk = k / (NVT * 128), t = (k >> 7) % NVT, kb2 = (k >> 6) & 1, ln = k & 63;
+        const int row = 16 * blk + 8 * kb2 + (ln >> 4), col = 16 * t + (ln & 15);
+        sgr[row][col] = v.x;
+        sgr[row + 4][col] = v.y;
+    }
+}
+// a lane's column sums of tile t, block column cb + lc of strip I: pairs (o[0], o[1]) -> p = 8 t + lr, (o[2], o[3]) -> p + 4
+__device__ __forceinline__ void pk_store_colsums(double* __restrict__ colpart2, long long colpart_stride, long long I, long long n,
+                                                 long long c, int t, int lr, int lv, const double4_t& dc) {
+    const int p0 = 8 * t + lr;
+    double* q = colpart2 + 2 * ((long long)p0 * colpart_stride + I * n + c);
+    if (2 * p0 < lv) *reinterpret_cast<double2_t*>(q) = double2_t{dc.x, dc.y};
+    if (2 * (p0 + 4) < lv) *reinterpret_cast<double2_t*>(q + 8 * colpart_stride) = double2_t{dc.z, dc.w};
+}
+
 // Round 4 tried the cross-block register pipeline here (loads of block b + 4, and b + 8, in flight behind the 32 MFMAs of block
 // b, wave-uniform row addresses through the scalar unit): at two waves per SIMD the 256 registers do not hold a second 8 KiB
 // block beside gr / dr / the LDS reads in flight -- 336-490 bytes of scratch per lane, 0.65 ms per pass against 0.31
@@ -1100,7 +1171,7 @@ __global__ __launch_bounds__(256) void k_pack_grads(const double* __restrict__ g
 // loads are buffered.  What did pay is how the tiles reach the CUs: k_symm_mfma_q below.
 //
 // One tile: strip I of the shard (rows r0 = row0 + 64 I ...), column segment J; sh = the workgroup's 4 x 64 x 17 doubles.
-template <bool NT, int SEG>
+template <bool NT, int SEG, bool PK = false>
 __device__ __forceinline__ void symm_tile(const double* __restrict__ Q, long long ld, long long n, long long row0, long long I,
                                           long long J, const double* __restrict__ gT, int lv, double* __restrict__ rowpart,
                                           double* __restrict__ colpart, long long rowpart_stride, long long colpart_stride,
@@ -1112,8 +1183,18 @@ __device__ __forceinline__ void symm_tile(const double* __restrict__ Q, long lon
     const bool full = c0 + SEG - 1 < r0;
     // A operand of the column product: gT rows of the strip
     double gr[16];
+    if constexpr (PK) {
 #pragma unroll
-    for (int j = 0; j < 16; ++j) gr[j] = gT[(r0 + 4 * j + lr) * SMM_NV + lc];
+        for (int jq = 0; jq < 4; ++jq) {
+            double q4[4];
+            pk_load_gc<1>(gT, r0 + 16 * jq, 0, lane, q4);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) gr[4 * jq + k] = q4[k];
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < 16; ++j) gr[j] = gT[(r0 + 4 * j + lr) * SMM_NV + lc];
+    }
     double4_t dr[4];
 #pragma unroll
     for (int jj = 0; jj < 4; ++jj) dr[jj] = double4_t{0.0, 0.0, 0.0, 0.0};
@@ -1127,8 +1208,12 @@ __device__ __forceinline__ void symm_tile(const double* __restrict__ Q, long lon
         double x[16], gc[4];
 #pragma unroll
         for (int j = 0; j < 16; ++j) x[j] = ld_stream<NT, double>(qbase + (long long)(4 * j) * ld + cb);
+        if constexpr (PK) {
+            pk_load_gc<1>(gT, cb, 0, lane, gc);
+        } else {
 #pragma unroll
-        for (int kb = 0; kb < 4; ++kb) gc[kb] = gT[(cb + 4 * kb + lr) * SMM_NV + lc];
+            for (int kb = 0; kb < 4; ++kb) gc[kb] = gT[(cb + 4 * kb + lr) * SMM_NV + lc];
+        }
         const bool diag = !full && cb + 15 >= r0;  // some element of the block is on or right of the diagonal
         double4_t dc = {0.0, 0.0, 0.0, 0.0};
         if (diag) {
@@ -1152,11 +1237,15 @@ __device__ __forceinline__ void symm_tile(const double* __restrict__ Q, long lon
                 const double t = mysh[(16 * jj + lc) * SMM_PITCH + 4 * kb + lr];
                 dr[jj] = __builtin_amdgcn_mfma_f64_16x16x4f64(gc[kb], t, dr[jj], 0, 0, 0);
             }
-        const double o[4] = {dc.x, dc.y, dc.z, dc.w};
+        if constexpr (PK) {
+            pk_store_colsums(colpart, colpart_stride, I, n, cb + lc, 0, lr, lv, dc);
+        } else {
+            const double o[4] = {dc.x, dc.y, dc.z, dc.w};
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int v = lr + 4 * i;
-            if (v < lv) colpart[(long long)v * colpart_stride + I * n + cb + lc] = o[i];
+            for (int i = 0; i < 4; ++i) {
+                const int v = lr + 4 * i;
+                if (v < lv) colpart[(long long)v * colpart_stride + I * n + cb + lc] = o[i];
+            }
         }
     }
     // row sums of the four waves, in wave order
@@ -1172,7 +1261,7 @@ __device__ __forceinline__ void symm_tile(const double* __restrict__ Q, long lon
     // thread (wave, lane) takes row group jj = wave: rows 16 wave + lc, vectors lr + 4 i
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-        const int v = lr + 4 * i;
+        const int v = PK ? pk_vec(0, lr + 4 * i) : lr + 4 * i;
         const int jj = wave;
         const double s0 = red[((0 * 4 + jj) * 4 + i) * 64 + lane], s1 = red[((1 * 4 + jj) * 4 + i) * 64 + lane];
         const double s2 = red[((2 * 4 + jj) * 4 + i) * 64 + lane], s3 = red[((3 * 4 + jj) * 4 + i) * 64 + lane];
@@ -1206,7 +1295,7 @@ __global__ __launch_bounds__(256) void k_symm_mfma(const double* __restrict__ Q,
 struct SymmTile {
     int I, J;  // strip of the shard, column segment
 };
-template <bool NT, int SEG>
+template <bool NT, int SEG, bool PK = false>  // PK: gT = gP, colpart = colpart2 (k_pack_operands)
 __global__ __launch_bounds__(256) void k_symm_mfma_q(const double* __restrict__ Q, long long ld, long long n, long long row0,
                                                      const double* __restrict__ gT, int lv, double* __restrict__ rowpart,
                                                      double* __restrict__ colpart, long long rowpart_stride,
@@ -1226,8 +1315,8 @@ __global__ __launch_bounds__(256) void k_symm_mfma_q(const double* __restrict__ 
         __syncthreads();
         const int t = s_t;
         if (t < 0) return;  // (uniform)
-        symm_tile<NT, SEG>(Q, ld, n, row0, (long long)tiles[t].I, (long long)tiles[t].J, gT, lv, rowpart, colpart, rowpart_stride,
-                           colpart_stride, sh);
+        symm_tile<NT, SEG, PK>(Q, ld, n, row0, (long long)tiles[t].I, (long long)tiles[t].J, gT, lv, rowpart, colpart, rowpart_stride,
+                               colpart_stride, sh);
     }
 }
 
@@ -1238,7 +1327,7 @@ __global__ __launch_bounds__(256) void k_symm_mfma_q(const double* __restrict__ 
 // k_symm_mfma's: the partial sums of 32 gradients are bit-identical to those of two 16-wide passes, in 0.445 ms against 0.55-0.62
 // (n = 16384, tools/experiments/symm32_queue.hip).
 constexpr int SMM_NV2 = 2 * SMM_NV;
-template <bool NT, int SEG>
+template <bool NT, int SEG, bool PK = false>
 __device__ __forceinline__ void symm_tile2(const double* __restrict__ Q, long long ld, long long n, long long row0, long long I,
                                            long long J, const double* __restrict__ gT, int lv, double* __restrict__ rowpart,
                                            double* __restrict__ colpart, long long rowpart_stride, long long colpart_stride,
@@ -1248,7 +1337,11 @@ __device__ __forceinline__ void symm_tile2(const double* __restrict__ Q, long lo
     const long long r0 = row0 + I * SYMV_H;
     const long long c0 = J * SEG;
     const bool full = c0 + SEG - 1 < r0;
-    for (int k = threadIdx.x; k < SYMV_H * SMM_NV2; k += 256) sgr[k / SMM_NV2][k % SMM_NV2] = gT[(r0 + k / SMM_NV2) * SMM_NV2 + k % SMM_NV2];
+    if constexpr (PK) {
+        pk_stage_sgr<2>(gT, r0, sgr);
+    } else {
+        for (int k = threadIdx.x; k < SYMV_H * SMM_NV2; k += 256) sgr[k / SMM_NV2][k % SMM_NV2] = gT[(r0 + k / SMM_NV2) * SMM_NV2 + k % SMM_NV2];
+    }
     __syncthreads();
     double4_t dr[2][4];
 #pragma unroll
@@ -1265,9 +1358,14 @@ __device__ __forceinline__ void symm_tile2(const double* __restrict__ Q, long lo
 #pragma unroll
         for (int j = 0; j < 16; ++j) x[j] = ld_stream<NT, double>(qbase + (long long)(4 * j) * ld + cb);
 #pragma unroll
-        for (int t = 0; t < 2; ++t)
+        for (int t = 0; t < 2; ++t) {
+            if constexpr (PK) {
+                pk_load_gc<2>(gT, cb, t, lane, gc[t]);
+            } else {
 #pragma unroll
-            for (int kb = 0; kb < 4; ++kb) gc[t][kb] = gT[(cb + 4 * kb + lr) * SMM_NV2 + 16 * t + lc];
+                for (int kb = 0; kb < 4; ++kb) gc[t][kb] = gT[(cb + 4 * kb + lr) * SMM_NV2 + 16 * t + lc];
+            }
+        }
         const bool diag = !full && cb + 15 >= r0;
         double4_t dc[2] = {double4_t{0.0, 0.0, 0.0, 0.0}, double4_t{0.0, 0.0, 0.0, 0.0}};
 #pragma unroll
@@ -1298,11 +1396,15 @@ __device__ __forceinline__ void symm_tile2(const double* __restrict__ Q, long lo
                 }
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
-            const double o[4] = {dc[t].x, dc[t].y, dc[t].z, dc[t].w};
+            if constexpr (PK) {
+                pk_store_colsums(colpart, colpart_stride, I, n, cb + lc, t, lr, lv, dc[t]);
+            } else {
+                const double o[4] = {dc[t].x, dc[t].y, dc[t].z, dc[t].w};
 #pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int v = 16 * t + lr + 4 * i;
-                if (v < lv) colpart[(long long)v * colpart_stride + I * n + cb + lc] = o[i];
+                for (int i = 0; i < 4; ++i) {
+                    const int v = 16 * t + lr + 4 * i;
+                    if (v < lv) colpart[(long long)v * colpart_stride + I * n + cb + lc] = o[i];
+                }
             }
         }
     }
@@ -1319,7 +1421,7 @@ __device__ __forceinline__ void symm_tile2(const double* __restrict__ Q, long lo
         __syncthreads();
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            const int v = 16 * t + lr + 4 * i;
+            const int v = PK ? pk_vec(t, lr + 4 * i) : 16 * t + lr + 4 * i;
             const int jj = wave;
             const double s0 = red[((0 * 4 + jj) * 4 + i) * 64 + lane], s1 = red[((1 * 4 + jj) * 4 + i) * 64 + lane];
             const double s2 = red[((2 * 4 + jj) * 4 + i) * 64 + lane], s3 = red[((3 * 4 + jj) * 4 + i) * 64 + lane];
@@ -1329,7 +1431,7 @@ __device__ __forceinline__ void symm_tile2(const double* __restrict__ Q, long lo
     }
 }
 
-template <bool NT, int SEG>
+template <bool NT, int SEG, bool PK = false>
 __global__ __launch_bounds__(256, 2) void k_symm_mfma_q2(const double* __restrict__ Q, long long ld, long long n, long long row0,
                                                          const double* __restrict__ gT, int lv, double* __restrict__ rowpart,
                                                          double* __restrict__ colpart, long long rowpart_stride,
@@ -1350,8 +1452,8 @@ __global__ __launch_bounds__(256, 2) void k_symm_mfma_q2(const double* __restric
         __syncthreads();
         const int t = s_t;
         if (t < 0) return;
-        symm_tile2<NT, SEG>(Q, ld, n, row0, (long long)tiles[t].I, (long long)tiles[t].J, gT, lv, rowpart, colpart, rowpart_stride,
-                            colpart_stride, sh, sgr);
+        symm_tile2<NT, SEG, PK>(Q, ld, n, row0, (long long)tiles[t].I, (long long)tiles[t].J, gT, lv, rowpart, colpart,
+                                rowpart_stride, colpart_stride, sh, sgr);
     }
 }
 
@@ -1372,13 +1474,13 @@ __global__ __launch_bounds__(256, 2) void k_symm_mfma_q2(const double* __restric
 // kernels do nothing once it has.  Here: the update always, the products only while st->halted is clear.
 // Unsharded handles only (row0 = 0, n % 64 == 0: every strip full, so k_apply_mfma's row and column limits never cut a block).
 // LDS: sh (34 KiB) + sgr (16.5 KiB) + the strip's A operands (64 NP doubles: 24 KiB at NP = 48) -- two workgroups per CU.
-template <int NP, bool NT, int SEG, bool WIDE>
+template <int NP, bool NT, int SEG, bool WIDE, bool PK = false>
 __device__ __forceinline__ void apply_symm_tile(double* __restrict__ Q, long long ld, long long n, long long I, long long J,
                                                 const double* __restrict__ pend, const double* __restrict__ cpend,
                                                 const double* __restrict__ gT, int lv, double* __restrict__ rowpart,
                                                 double* __restrict__ colpart, long long rowpart_stride, long long colpart_stride,
                                                 bool prod, double (*sh)[SYMV_H * SMM_PITCH], double (*sgr)[SMM_NV2 + 1],
-                                                double* __restrict__ sa) {
+                                                double* __restrict__ sa, const double* __restrict__ pendP) {
     constexpr int KS = NP / 4;
     constexpr int NVT = WIDE ? 2 : 1;      // 16-wide column tiles of the product
     constexpr int NVW = SMM_NV * NVT;      // row pitch of gT
@@ -1394,8 +1496,13 @@ __device__ __forceinline__ void apply_symm_tile(double* __restrict__ Q, long lon
         const int k = 4 * s + (ln >> 4);
         sa[((q * (KS / 2) + s / 2) * 64 + ln) * 2 + (s & 1)] = -(cpend[k] * pend[(long long)k * n + r0 + 16 * q + (ln & 15)]);
     }
-    if (prod)
-        for (int k = threadIdx.x; k < SYMV_H * NVW; k += 256) sgr[k / NVW][k % NVW] = gT[(r0 + k / NVW) * NVW + k % NVW];
+    if (prod) {
+        if constexpr (PK) {
+            pk_stage_sgr<NVT>(gT, r0, sgr);
+        } else {
+            for (int k = threadIdx.x; k < SYMV_H * NVW; k += 256) sgr[k / NVW][k % NVW] = gT[(r0 + k / NVW) * NVW + k % NVW];
+        }
+    }
     __syncthreads();
     double4_t dr[NVT][4];
 #pragma unroll
@@ -1412,8 +1519,17 @@ __device__ __forceinline__ void apply_symm_tile(double* __restrict__ Q, long lon
         double x[16], bv[KS], gc[NVT][4];
 #pragma unroll
         for (int j = 0; j < 16; ++j) x[j] = ld_stream<NT, double>(qbase + (long long)(4 * j) * ld + cb);
+        if constexpr (PK) {
+            const double2_t* pp = reinterpret_cast<const double2_t*>(pendP) + (cb >> 4) * (KS / 2) * 64 + lane;
 #pragma unroll
-        for (int s = 0; s < KS; ++s) bv[s] = pbase[(long long)(4 * s) * n + cb];
+            for (int s2 = 0; s2 < KS / 2; ++s2) {
+                const double2_t v = pp[s2 * 64];
+                bv[2 * s2] = v.x, bv[2 * s2 + 1] = v.y;
+            }
+        } else {
+#pragma unroll
+            for (int s = 0; s < KS; ++s) bv[s] = pbase[(long long)(4 * s) * n + cb];
+        }
         // (the phases are kept apart: with the row-sum accumulators live across the loop, 256 registers hold one phase's
         // operands at a time, not the scheduler's hoisted loads of all three)
         __builtin_amdgcn_sched_barrier(0);
@@ -1444,9 +1560,14 @@ __device__ __forceinline__ void apply_symm_tile(double* __restrict__ Q, long lon
         __builtin_amdgcn_sched_barrier(0);
         // 3. the products, as symm_tile2 forms them
 #pragma unroll
-        for (int t = 0; t < NVT; ++t)
+        for (int t = 0; t < NVT; ++t) {
+            if constexpr (PK) {
+                pk_load_gc<NVT>(gT, cb, t, lane, gc[t]);
+            } else {
 #pragma unroll
-            for (int kb = 0; kb < 4; ++kb) gc[t][kb] = gT[(cb + 4 * kb + lr) * NVW + 16 * t + lc];
+                for (int kb = 0; kb < 4; ++kb) gc[t][kb] = gT[(cb + 4 * kb + lr) * NVW + 16 * t + lc];
+            }
+        }
         const bool diag = !full && cb + 15 >= r0;
         double4_t dc[NVT];
 #pragma unroll
@@ -1479,11 +1600,15 @@ __device__ __forceinline__ void apply_symm_tile(double* __restrict__ Q, long lon
                 }
 #pragma unroll
         for (int t = 0; t < NVT; ++t) {
-            const double o[4] = {dc[t].x, dc[t].y, dc[t].z, dc[t].w};
+            if constexpr (PK) {
+                pk_store_colsums(colpart, colpart_stride, I, n, cb + lc, t, lr, lv, dc[t]);
+            } else {
+                const double o[4] = {dc[t].x, dc[t].y, dc[t].z, dc[t].w};
 #pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int v = 16 * t + lr + 4 * i;
-                if (v < lv) colpart[(long long)v * colpart_stride + I * n + cb + lc] = o[i];
+                for (int i = 0; i < 4; ++i) {
+                    const int v = 16 * t + lr + 4 * i;
+                    if (v < lv) colpart[(long long)v * colpart_stride + I * n + cb + lc] = o[i];
+                }
             }
         }
     }
@@ -1501,7 +1626,7 @@ __device__ __forceinline__ void apply_symm_tile(double* __restrict__ Q, long lon
         __syncthreads();
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            const int v = 16 * t + lr + 4 * i;
+            const int v = PK ? pk_vec(t, lr + 4 * i) : 16 * t + lr + 4 * i;
             const int jj = wave;
             const double s0 = red[((0 * 4 + jj) * 4 + i) * 64 + lane], s1 = red[((1 * 4 + jj) * 4 + i) * 64 + lane];
             const double s2 = red[((2 * 4 + jj) * 4 + i) * 64 + lane], s3 = red[((3 * 4 + jj) * 4 + i) * 64 + lane];
@@ -1511,14 +1636,15 @@ __device__ __forceinline__ void apply_symm_tile(double* __restrict__ Q, long lon
     }
 }
 
-template <int NP, bool NT, int SEG, bool WIDE>
+template <int NP, bool NT, int SEG, bool WIDE, bool PK = false>  // PK: gT = gP, colpart = colpart2, pendP as k_pack_operands leaves them
 __global__ __launch_bounds__(256, 2) void k_apply_symm_q(double* __restrict__ Q, long long ld, long long n,
                                                          const double* __restrict__ pend, const double* __restrict__ cpend,
                                                          const double* __restrict__ gT, int lv, double* __restrict__ rowpart,
                                                          double* __restrict__ colpart, long long rowpart_stride,
                                                          long long colpart_stride, const DevState* __restrict__ st,
                                                          const SymmTile* __restrict__ tiles, int ntiles,
-                                                         unsigned* __restrict__ queue) {
+                                                         unsigned* __restrict__ queue,
+                                                         const double* __restrict__ pendP = nullptr) {
     static_assert(NP % 8 == 0, "k-steps taken in pairs");
     __shared__ double sh[4][SYMV_H * SMM_PITCH];
     __shared__ double sgr[SYMV_H][SMM_NV2 + 1];
@@ -1534,8 +1660,8 @@ __global__ __launch_bounds__(256, 2) void k_apply_symm_q(double* __restrict__ Q,
         __syncthreads();
         const int t = s_t;
         if (t < 0) return;  // (uniform)
-        apply_symm_tile<NP, NT, SEG, WIDE>(Q, ld, n, (long long)tiles[t].I, (long long)tiles[t].J, pend, cpend, gT, lv, rowpart,
-                                           colpart, rowpart_stride, colpart_stride, prod, sh, sgr, sa);
+        apply_symm_tile<NP, NT, SEG, WIDE, PK>(Q, ld, n, (long long)tiles[t].I, (long long)tiles[t].J, pend, cpend, gT, lv, rowpart,
+                                               colpart, rowpart_stride, colpart_stride, prod, sh, sgr, sa, pendP);
     }
 }
 

@@ -83,6 +83,7 @@ struct Defaults {
     int lookahead = 32;        // ELLHIP_OPT_LOOKAHEAD
     int queue_depth = 48;      // ELLHIP_OPT_QUEUE_DEPTH
     int apply_symm = 1;        // ELLHIP_OPT_APPLY_SYMM
+    int packed_operands = 1;   // ELLHIP_OPT_PACKED_OPERANDS
     int stable_solve = 3;      // ELLHIP_OPT_STABLE_SOLVE
     int stable_factor = 2;     // ELLHIP_OPT_STABLE_FACTOR
     int pad = -1;              // ELLHIP_OPT_PAD: extra doubles per row of Q; -1 = by size (create_impl)
@@ -153,6 +154,9 @@ struct ellhip_space {
     double* d_rowpart_m = nullptr;   // [MULTI_MAX][nsegs][n]
     double* d_colpart_m = nullptr;   // [MULTI_MAX][nstrips][n]
     double* d_gT = nullptr;          // [n][16]: a group's gradients side by side (operand layout of k_symm_mfma)
+    int packed_operands = 1;         // the matrix-core passes fetch gradients and recorded vectors, and store column sums, 16 bytes per lane
+                                     // (k_pack_operands: gP in d_gT, colpart2 in d_colpart_m; unsharded handles)
+    double* d_pendP = nullptr;       // [n / 16][KS / 2][64][2]: the recorded vectors in the fused pass' operand order (MAXPEND n doubles)
     SymmTile* d_symm_tiles = nullptr;  // k_symm_mfma_q's tiles, largest first
     unsigned* d_symm_queue = nullptr;  // its two counters (one per half of the partial-sum sets), 128 bytes apart
     int symm_ntiles = 0, symm_wgs = 0;
@@ -340,6 +344,7 @@ void pick_shape(ellhip_space* s) {
     s->lookahead = g_defaults.lookahead;
     s->queue_depth = g_defaults.queue_depth;
     s->apply_symm = g_defaults.apply_symm;
+    s->packed_operands = g_defaults.packed_operands;
     s->resident = g_defaults.resident;
     s->stable_solve = g_defaults.stable_solve;
     s->stable_factor = g_defaults.stable_factor;
@@ -1582,7 +1587,7 @@ bool multi_shard_ok(const ellhip_space* s) {
 constexpr int MULTI_NO_MEMORY = 1;  // multi_setup: the buffers do not fit; the handle has been switched to lookahead 1
 
 void multi_free(ellhip_space* s) {
-    double** bufs[] = {&s->d_rowpart_m, &s->d_colpart_m, &s->d_gT, &s->d_grpY, &s->d_gpart, &s->d_cpart, &s->d_gsums};
+    double** bufs[] = {&s->d_rowpart_m, &s->d_colpart_m, &s->d_gT, &s->d_pendP, &s->d_grpY, &s->d_gpart, &s->d_cpart, &s->d_gsums};
     for (double** b : bufs) {
         if (*b) (void)hipFree(*b);
         *b = nullptr;
@@ -1609,6 +1614,7 @@ int multi_setup(ellhip_space* s) {
     hipError_t e = hipMalloc(&s->d_rowpart_m, rbytes);
     if (e == hipSuccess) e = hipMalloc(&s->d_colpart_m, cbytes);
     if (e == hipSuccess) e = hipMalloc(&s->d_gT, (size_t)2 * s->n * MULTI_MAX * sizeof(double));
+    if (e == hipSuccess && !s->sharded) e = hipMalloc(&s->d_pendP, (size_t)MAXPEND * (size_t)s->n * sizeof(double));
     if (e == hipSuccess) e = hipMalloc(&s->d_grpY, (size_t)GRP_MAX * (size_t)s->n * sizeof(double));
     if (e == hipSuccess) e = hipMalloc(&s->d_gpart, (size_t)GRP_MAX * nb * (MAXPEND + 1) * sizeof(double));
     if (e == hipSuccess) e = hipMalloc(&s->d_cpart, nb * GRP_MAX * GRP_MAX * sizeof(double));
@@ -1659,32 +1665,37 @@ int multi_setup(ellhip_space* s) {
     hipLaunchKernelGGL((__VA_ARGS__), dim3(1), dim3(256), 0, s->stream, (const double*)s->d_Q, s->ld, s->n, s->row0,                 \
                        (const double*)s->d_gT, 0, s->d_rowpart_m, s->d_colpart_m, (long long)rowpart_elems(s),                      \
                        (long long)colpart_elems(s), (const DevState*)s->d_st, (const SymmTile*)s->d_symm_tiles, 0, s->d_symm_queue)
-        if (wide && nt) {
-            ELLHIP_SYMM_WARM(k_symm_mfma_q<true, SYMV_SEG>);
-            ELLHIP_SYMM_WARM(k_symm_mfma_q2<true, SYMV_SEG>);
-        } else if (wide) {
-            ELLHIP_SYMM_WARM(k_symm_mfma_q<false, SYMV_SEG>);
-            ELLHIP_SYMM_WARM(k_symm_mfma_q2<false, SYMV_SEG>);
-        } else if (nt) {
-            ELLHIP_SYMM_WARM(k_symm_mfma_q<true, SYMV_SEG_SMALL>);
-            ELLHIP_SYMM_WARM(k_symm_mfma_q2<true, SYMV_SEG_SMALL>);
-        } else {
-            ELLHIP_SYMM_WARM(k_symm_mfma_q<false, SYMV_SEG_SMALL>);
-            ELLHIP_SYMM_WARM(k_symm_mfma_q2<false, SYMV_SEG_SMALL>);
-        }
+#define ELLHIP_SYMM_WARM2(NTV, SEGV)                            \
+    do {                                                        \
+        ELLHIP_SYMM_WARM(k_symm_mfma_q<NTV, SEGV>);             \
+        ELLHIP_SYMM_WARM(k_symm_mfma_q2<NTV, SEGV>);            \
+        if (!s->sharded) {  /* ELLHIP_OPT_PACKED_OPERANDS */    \
+            ELLHIP_SYMM_WARM(k_symm_mfma_q<NTV, SEGV, true>);   \
+            ELLHIP_SYMM_WARM(k_symm_mfma_q2<NTV, SEGV, true>);  \
+        }                                                       \
+    } while (0)
+        if (wide && nt) ELLHIP_SYMM_WARM2(true, SYMV_SEG);
+        else if (wide) ELLHIP_SYMM_WARM2(false, SYMV_SEG);
+        else if (nt) ELLHIP_SYMM_WARM2(true, SYMV_SEG_SMALL);
+        else ELLHIP_SYMM_WARM2(false, SYMV_SEG_SMALL);
+#undef ELLHIP_SYMM_WARM2
 #undef ELLHIP_SYMM_WARM
         // (and the fused apply + product passes, ELLHIP_OPT_APPLY_SYMM)
 #define ELLHIP_APPLY_SYMM_WARM(...)                                                                                                  \
     hipLaunchKernelGGL((__VA_ARGS__), dim3(1), dim3(256), 0, s->stream, s->d_Q, s->ld, s->n, (const double*)s->d_pend,               \
                        (const double*)s->d_cpend, (const double*)s->d_gT, 0, s->d_rowpart_m, s->d_colpart_m,                         \
                        (long long)rowpart_elems(s), (long long)colpart_elems(s), (const DevState*)s->d_st,                         \
-                       (const SymmTile*)s->d_symm_tiles, 0, s->d_symm_queue)
+                       (const SymmTile*)s->d_symm_tiles, 0, s->d_symm_queue, (const double*)s->d_pendP)
 #define ELLHIP_APPLY_SYMM_WARM4(NTV, SEGV)                         \
     do {                                                           \
         ELLHIP_APPLY_SYMM_WARM(k_apply_symm_q<MAXPEND, NTV, SEGV, true>);  \
         ELLHIP_APPLY_SYMM_WARM(k_apply_symm_q<MAXPEND, NTV, SEGV, false>); \
         ELLHIP_APPLY_SYMM_WARM(k_apply_symm_q<24, NTV, SEGV, true>);       \
         ELLHIP_APPLY_SYMM_WARM(k_apply_symm_q<24, NTV, SEGV, false>);      \
+        ELLHIP_APPLY_SYMM_WARM(k_apply_symm_q<MAXPEND, NTV, SEGV, true, true>);  \
+        ELLHIP_APPLY_SYMM_WARM(k_apply_symm_q<MAXPEND, NTV, SEGV, false, true>); \
+        ELLHIP_APPLY_SYMM_WARM(k_apply_symm_q<24, NTV, SEGV, true, true>);       \
+        ELLHIP_APPLY_SYMM_WARM(k_apply_symm_q<24, NTV, SEGV, false, true>);      \
     } while (0)
         if (s->row0 == 0 && !s->sharded) {
             if (wide && nt) ELLHIP_APPLY_SYMM_WARM4(true, SYMV_SEG);
@@ -1698,6 +1709,10 @@ int multi_setup(ellhip_space* s) {
     }
     return 0;
 }
+
+// ELLHIP_OPT_PACKED_OPERANDS: the passes of this handle's group runs take the packed forms (a queue run keeps one form from its
+// first pass to its last stage: the option is read here only, and set between runs).  Row shards stay on the unpacked kernels.
+bool packed_on(const ellhip_space* s) { return s->packed_operands != 0 && !s->sharded && s->symm_ntiles > 0 && s->d_pendP != nullptr; }
 
 // the scalar stage of a group whose products sit in the partial-sum sets 2 .. 2 + g - 1 (group_kernels.hpp)
 // phase 0: the reductions (they read the pass' partial sums at HBM rate and want the whole card); phase 1: the rest (Gram slices,
@@ -1714,6 +1729,10 @@ int group_stage_go(ellhip_space* s, long long i, int g, int half, int phase) {
             hipLaunchKernelGGL(k_group_reduce<0>, dim3(nb, (unsigned)g), dim3(256), 0, s->stream, s->n, s->row0, s->nrows,
                                (long long)s->symv_seg, rowp, colp, (long long)rowpart_elems(s), (long long)colpart_elems(s),
                                s->d_grpY, grads, s->n, (const double*)s->d_pend, s->d_gpart, (const DevState*)s->d_st);
+        else if (packed_on(s))  // (the pass of this group stored its column sums in pairs)
+            hipLaunchKernelGGL(k_group_reduce_p<NP>, dim3(nb, (unsigned)(g + 1) / 2), dim3(256), 0, s->stream, s->n, s->row0, s->nrows,
+                               (long long)s->symv_seg, rowp, colp, (long long)rowpart_elems(s), (long long)colpart_elems(s),
+                               s->d_grpY, grads, s->n, (const double*)s->d_pend, s->d_gpart, (const DevState*)s->d_st, g, s->npend);
         else
             hipLaunchKernelGGL(k_group_reduce<NP>, dim3(nb, (unsigned)g), dim3(256), 0, s->stream, s->n, s->row0, s->nrows,
                                (long long)s->symv_seg, rowp, colp, (long long)rowpart_elems(s), (long long)colpart_elems(s),
@@ -1754,17 +1773,26 @@ void symm_mfma_go(ellhip_space* s, const double* g_dev, int lv, hipStream_t st, 
     double* colp = s->d_colpart_m + (size_t)half * MULTI_MAX * colpart_elems(s);
     unsigned* queue = s->d_symm_queue + 32 * half;
     const int nvw = lv > SMM_NV ? SMM_NV2 : SMM_NV;  // one or two 16-wide column tiles
-    hipLaunchKernelGGL(k_pack_grads, dim3((unsigned)((s->n * nvw + 255) / 256)), dim3(256), 0, st, g_dev, s->n, lv, s->n, gT, queue, nvw);
+    const bool pk = packed_on(s);
+    if (pk)
+        hipLaunchKernelGGL(k_pack_operands, dim3((unsigned)(s->n * (nvw / SMM_NV) / 32)), dim3(256), 0, st, g_dev, s->n, lv, s->n, gT, queue,
+                           nvw / SMM_NV, (const double*)nullptr, (double*)nullptr, 0);
+    else
+        hipLaunchKernelGGL(k_pack_grads, dim3((unsigned)((s->n * nvw + 255) / 256)), dim3(256), 0, st, g_dev, s->n, lv, s->n, gT, queue, nvw);
     const bool nt = s->sh_gemv.nt != 0;
 #define ELLHIP_SYMM_Q(...)                                                                                                          \
     hipLaunchKernelGGL((__VA_ARGS__), dim3((unsigned)wgs), dim3(256), 0, st, (const double*)s->d_Q, s->ld, s->n, s->row0,                \
                        (const double*)gT, lv, rowp, colp, (long long)rowpart_elems(s), (long long)colpart_elems(s),                 \
                        (const DevState*)s->d_st, (const SymmTile*)s->d_symm_tiles, s->symm_ntiles, queue)
     if (nvw == SMM_NV) {
-        if (nt) ELLHIP_SYMM_Q(k_symm_mfma_q<true, SEG>);
+        if (pk && nt) ELLHIP_SYMM_Q(k_symm_mfma_q<true, SEG, true>);
+        else if (pk) ELLHIP_SYMM_Q(k_symm_mfma_q<false, SEG, true>);
+        else if (nt) ELLHIP_SYMM_Q(k_symm_mfma_q<true, SEG>);
         else ELLHIP_SYMM_Q(k_symm_mfma_q<false, SEG>);
     } else {
-        if (nt) ELLHIP_SYMM_Q(k_symm_mfma_q2<true, SEG>);
+        if (pk && nt) ELLHIP_SYMM_Q(k_symm_mfma_q2<true, SEG, true>);
+        else if (pk) ELLHIP_SYMM_Q(k_symm_mfma_q2<false, SEG, true>);
+        else if (nt) ELLHIP_SYMM_Q(k_symm_mfma_q2<true, SEG>);
         else ELLHIP_SYMM_Q(k_symm_mfma_q2<false, SEG>);
     }
 #undef ELLHIP_SYMM_Q
@@ -1791,20 +1819,29 @@ void apply_symm_mfma_go(ellhip_space* s, const double* g_dev, int lv, int half, 
     double* colp = s->d_colpart_m + (size_t)half * MULTI_MAX * colpart_elems(s);
     unsigned* queue = s->d_symm_queue + 32 * half;
     const int nvw = lv > SMM_NV ? SMM_NV2 : SMM_NV;
-    hipLaunchKernelGGL(k_pack_grads, dim3((unsigned)((s->n * nvw + 255) / 256)), dim3(256), 0, s->stream, g_dev, s->n, lv, s->n, gT,
-                       queue, nvw);
+    const bool pk = packed_on(s);
+    if (pk)  // (the gradients and -- every slot of pend is complete: the previous group's stage is ahead on this stream -- the recorded vectors)
+        hipLaunchKernelGGL(k_pack_operands, dim3((unsigned)(s->n * (nvw / SMM_NV) / 32 + s->n * (np / 8) / 64)), dim3(256), 0, s->stream, g_dev,
+                           s->n, lv, s->n, gT, queue, nvw / SMM_NV, (const double*)s->d_pend, s->d_pendP, np / 8);
+    else
+        hipLaunchKernelGGL(k_pack_grads, dim3((unsigned)((s->n * nvw + 255) / 256)), dim3(256), 0, s->stream, g_dev, s->n, lv, s->n, gT,
+                           queue, nvw);
     const bool nt = s->sh_gemv.nt != 0;
 #define ELLHIP_APPLY_SYMM(...)                                                                                                      \
     hipLaunchKernelGGL((__VA_ARGS__), dim3((unsigned)s->symm_wgs), dim3(256), 0, s->stream, s->d_Q, s->ld, s->n,                    \
                        (const double*)s->d_pend, (const double*)s->d_cpend, (const double*)gT, lv, rowp, colp,                      \
                        (long long)rowpart_elems(s), (long long)colpart_elems(s), (const DevState*)s->d_st,                         \
-                       (const SymmTile*)s->d_symm_tiles, s->symm_ntiles, queue)
+                       (const SymmTile*)s->d_symm_tiles, s->symm_ntiles, queue, (const double*)s->d_pendP)
 #define ELLHIP_APPLY_SYMM_NP(NPV)                                                                                                   \
     if (nvw == SMM_NV) {                                                                                                            \
-        if (nt) ELLHIP_APPLY_SYMM(k_apply_symm_q<NPV, true, SEG, false>);                                                           \
+        if (pk && nt) ELLHIP_APPLY_SYMM(k_apply_symm_q<NPV, true, SEG, false, true>);                                               \
+        else if (pk) ELLHIP_APPLY_SYMM(k_apply_symm_q<NPV, false, SEG, false, true>);                                               \
+        else if (nt) ELLHIP_APPLY_SYMM(k_apply_symm_q<NPV, true, SEG, false>);                                                      \
         else ELLHIP_APPLY_SYMM(k_apply_symm_q<NPV, false, SEG, false>);                                                             \
     } else {                                                                                                                        \
-        if (nt) ELLHIP_APPLY_SYMM(k_apply_symm_q<NPV, true, SEG, true>);                                                            \
+        if (pk && nt) ELLHIP_APPLY_SYMM(k_apply_symm_q<NPV, true, SEG, true, true>);                                                \
+        else if (pk) ELLHIP_APPLY_SYMM(k_apply_symm_q<NPV, false, SEG, true, true>);                                                \
+        else if (nt) ELLHIP_APPLY_SYMM(k_apply_symm_q<NPV, true, SEG, true>);                                                       \
         else ELLHIP_APPLY_SYMM(k_apply_symm_q<NPV, false, SEG, true>);                                                              \
     }
     if (np == MAXPEND) {
@@ -2240,6 +2277,7 @@ void ellhip_destroy(ellhip_space* s) {
     if (s->d_rowpart_m) (void)hipFree(s->d_rowpart_m);
     if (s->d_colpart_m) (void)hipFree(s->d_colpart_m);
     if (s->d_gT) (void)hipFree(s->d_gT);
+    if (s->d_pendP) (void)hipFree(s->d_pendP);
     if (s->d_grpY) (void)hipFree(s->d_grpY);
     if (s->d_gpart) (void)hipFree(s->d_gpart);
     if (s->d_cpart) (void)hipFree(s->d_cpart);
@@ -2298,6 +2336,7 @@ int ellhip_clone(const ellhip_space* src_c, ellhip_space** out) {
     s->lookahead = src->lookahead;
     s->queue_depth = src->queue_depth;
     s->apply_symm = src->apply_symm;
+    s->packed_operands = src->packed_operands;
     s->resident = src->resident;
     s->shard_symmetric = src->shard_symmetric;
     s->upper_stale = src->upper_stale;
@@ -2605,7 +2644,7 @@ int option_ok(int key, long long v) {
     switch (key) {
         case ELLHIP_OPT_APPLY_KERNEL:
             return (v >= -1 && v <= 2) ? 0 : fail(ELLHIP_E_INVALID, "option value must be -1, 0, 1 or 2");
-        case ELLHIP_OPT_STAGE_DIRECT: case ELLHIP_OPT_APPLY_SYMM:
+        case ELLHIP_OPT_STAGE_DIRECT: case ELLHIP_OPT_APPLY_SYMM: case ELLHIP_OPT_PACKED_OPERANDS:
             return (v == 0 || v == 1) ? 0 : fail(ELLHIP_E_INVALID, "option value must be 0 or 1");
         case ELLHIP_OPT_AUTO_DEFER: case ELLHIP_OPT_SYMV: case ELLHIP_OPT_APPLY_LOWER:
         case ELLHIP_OPT_FUSE_DOTS:
@@ -2644,6 +2683,7 @@ int ellhip_set_default_option(int key, int64_t value) {
         case ELLHIP_OPT_LOOKAHEAD: g_defaults.lookahead = (int)value; break;
         case ELLHIP_OPT_QUEUE_DEPTH: g_defaults.queue_depth = (int)value; break;
         case ELLHIP_OPT_APPLY_SYMM: g_defaults.apply_symm = (int)value; break;
+        case ELLHIP_OPT_PACKED_OPERANDS: g_defaults.packed_operands = (int)value; break;
         case ELLHIP_OPT_STABLE_SOLVE: g_defaults.stable_solve = (int)value; break;
         case ELLHIP_OPT_STABLE_FACTOR: g_defaults.stable_factor = (int)value; break;
         case ELLHIP_OPT_PAD: g_defaults.pad = (int)value; break;
@@ -2669,6 +2709,7 @@ int ellhip_default_option(int key, int64_t* value) {
         case ELLHIP_OPT_LOOKAHEAD: *value = g_defaults.lookahead; break;
         case ELLHIP_OPT_QUEUE_DEPTH: *value = g_defaults.queue_depth; break;
         case ELLHIP_OPT_APPLY_SYMM: *value = g_defaults.apply_symm; break;
+        case ELLHIP_OPT_PACKED_OPERANDS: *value = g_defaults.packed_operands; break;
         case ELLHIP_OPT_STABLE_SOLVE: *value = g_defaults.stable_solve; break;
         case ELLHIP_OPT_STABLE_FACTOR: *value = g_defaults.stable_factor; break;
         case ELLHIP_OPT_PAD: *value = g_defaults.pad; break;
@@ -2708,6 +2749,10 @@ int ellhip_set_option(ellhip_space* s, int key, int64_t value) {
         case ELLHIP_OPT_APPLY_SYMM:
             if (!ell) return fail(ELLHIP_E_INVALID, "this option exists on Ell only");
             s->apply_symm = (int)value;
+            return 0;
+        case ELLHIP_OPT_PACKED_OPERANDS:
+            if (!ell) return fail(ELLHIP_E_INVALID, "this option exists on Ell only");
+            s->packed_operands = (int)value;
             return 0;
         case ELLHIP_OPT_RESIDENT_FAULT:
             if (!ell) return fail(ELLHIP_E_INVALID, "this option exists on Ell only");
@@ -2761,6 +2806,7 @@ int ellhip_get_option(const ellhip_space* s, int key, int64_t* value) {
         case ELLHIP_OPT_LOOKAHEAD: *value = s->lookahead; break;
         case ELLHIP_OPT_QUEUE_DEPTH: *value = s->queue_depth; break;
         case ELLHIP_OPT_APPLY_SYMM: *value = s->apply_symm; break;
+        case ELLHIP_OPT_PACKED_OPERANDS: *value = s->packed_operands; break;
         case ELLHIP_OPT_RESIDENT_FAULT: *value = s->rs_fault_at; break;
         case ELLHIP_OPT_RESIDENT_ABANDONED: *value = s->rs_abandoned; break;
         case ELLHIP_OPT_STABLE_SOLVE: *value = s->stable_solve; break;

@@ -48,6 +48,135 @@ __global__ __launch_bounds__(256) void k_group_reduce(long long n, long long row
                                  colpart + l * colpart_stride, Y + l * n, g + l * g_stride, pend, gpart + l * nb * (NP + 1), part, slot0);
 }
 
+// ELLHIP_OPT_PACKED_OPERANDS: the same from the packed passes' column sums, colpart2[p][I][c][2] = those of cuts 2 p, 2 p + 1
+// side by side (ell_kernels.hpp, k_pack_operands).  One workgroup per pair (grid.y = p) and 128 columns; every addition of
+// symv_reduce_block<NP, false> is made in its order, so Y and gpart are word for word what k_group_reduce writes:
+//   - column sums: lane L of wave w takes columns 128 blk + L and 128 blk + 64 + L of both cuts (16-byte loads, 1 KiB per
+//     wave-instruction), each from its own first strip I0(c) + w in steps of four, and leaves the four sums in LDS;
+//   - wave 0 finishes cut 2 p and wave 1 cut 2 p + 1 on the old map (lane = columns 2 L, 2 L + 1): the row sums in segment order,
+//     + ((c0 + c1) + c2) + c3, y, g.y;
+//   - v_j.g: wave w takes j = w, w + 4, ... for both cuts (one load of v_j serves the two).
+// Unsharded handles (the dot products are formed here).  G = cuts of the group: an odd group's last pair has one.
+template <int NP>
+__global__ __launch_bounds__(256) void k_group_reduce_p(long long n, long long row0, long long nrows, long long seg,
+                                                        const double* __restrict__ rowpart,
+                                                        const double* __restrict__ colpart2, long long rowpart_stride,
+                                                        long long colpart_stride, double* __restrict__ Y,
+                                                        const double* __restrict__ g, long long g_stride,
+                                                        const double* __restrict__ pend, double* __restrict__ gpart,
+                                                        const DevState* __restrict__ st, int G, int slot0 = NP) {
+    static_assert(NP > 0, "row shards keep k_group_reduce<0>");
+    __shared__ alignas(16) double part[2][4][128];  // [cut of the pair][wave][column of the block]
+    if (st->halted) return;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long long p = blockIdx.y, nb = gridDim.x, blk = blockIdx.x;
+    const long long i = blk * 128 + 2 * lane;  // the old map's column pair
+    const long long nstrips = (nrows + SYMV_H - 1) / SYMV_H;
+    const bool two = 2 * p + 1 < G;
+    // operands of the dot products first: their latency hides behind the strip loop
+    constexpr int NPW = (NP + 3) / 4;
+    double2_t gi[2] = {{0.0, 0.0}, {0.0, 0.0}};
+    double2_t pv[NPW];
+    if (i < n) {
+        gi[0] = *reinterpret_cast<const double2_t*>(g + (2 * p) * g_stride + i);
+        if (two) gi[1] = *reinterpret_cast<const double2_t*>(g + (2 * p + 1) * g_stride + i);
+    }
+#pragma unroll
+    for (int k = 0; k < NPW; ++k) {
+        const int j = wave + 4 * k;
+        pv[k] = (i < n && j < NP && j < slot0) ? *reinterpret_cast<const double2_t*>(pend + (long long)j * n + i) : double2_t{0.0, 0.0};
+    }
+    const double* cp = colpart2 + 2 * p * colpart_stride;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const long long c = blk * 128 + 64 * h + lane;
+        double2_t s = {0.0, 0.0};  // .x: cut 2 p, .y: cut 2 p + 1
+        if (c < n) {
+            long long I = (c < row0 ? 0 : (c - row0) / SYMV_H) + wave;
+            for (; I + 60 < nstrips; I += 64) {
+                double2_t v[16];
+#pragma unroll
+                for (int u = 0; u < 16; ++u) v[u] = *reinterpret_cast<const double2_t*>(cp + 2 * ((I + 4 * u) * n + c));
+#pragma unroll
+                for (int u = 0; u < 16; ++u) {
+                    s.x += v[u].x;
+                    s.y += v[u].y;
+                }
+            }
+            for (; I + 28 < nstrips; I += 32) {
+                double2_t v[8];
+#pragma unroll
+                for (int u = 0; u < 8; ++u) v[u] = *reinterpret_cast<const double2_t*>(cp + 2 * ((I + 4 * u) * n + c));
+#pragma unroll
+                for (int u = 0; u < 8; ++u) {
+                    s.x += v[u].x;
+                    s.y += v[u].y;
+                }
+            }
+            for (; I < nstrips; I += 4) {
+                const double2_t v = *reinterpret_cast<const double2_t*>(cp + 2 * (I * n + c));
+                s.x += v.x;
+                s.y += v.y;
+            }
+        }
+        part[0][wave][64 * h + lane] = s.x;
+        part[1][wave][64 * h + lane] = s.y;
+    }
+    // row partial sums of this wave's cut (waves 0 and 1), requested before the barrier, added in segment order
+    const bool fin = wave == 0 || (wave == 1 && two);
+    const long long l = 2 * p + wave;
+    double2_t r = {0.0, 0.0};
+    if (fin && i < n && i >= row0 && i < row0 + nrows) {
+        const double* rp = rowpart + l * rowpart_stride;
+        const long long nJ = i / seg + 1;
+        for (long long J = 0; J < nJ; J += 8) {
+            double2_t v[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                const long long Ju = (J + u < nJ) ? J + u : nJ - 1;
+                v[u] = *reinterpret_cast<const double2_t*>(rp + Ju * n + i);
+            }
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                r.x += (J + u < nJ) ? v[u].x : 0.0;
+                r.y += (J + u < nJ) ? v[u].y : 0.0;
+            }
+        }
+    }
+    __syncthreads();
+    if (fin) {
+        double2_t yv = {0.0, 0.0};
+        if (i < n) {
+            const double2_t c0 = *reinterpret_cast<const double2_t*>(&part[wave][0][2 * lane]);
+            const double2_t c1 = *reinterpret_cast<const double2_t*>(&part[wave][1][2 * lane]);
+            const double2_t c2 = *reinterpret_cast<const double2_t*>(&part[wave][2][2 * lane]);
+            const double2_t c3 = *reinterpret_cast<const double2_t*>(&part[wave][3][2 * lane]);
+            r.x += ((c0.x + c1.x) + c2.x) + c3.x;
+            r.y += ((c0.y + c1.y) + c2.y) + c3.y;
+            *reinterpret_cast<double2_t*>(Y + l * n + i) = r;
+            yv = r;
+        }
+        const double2_t gl = wave == 0 ? gi[0] : gi[1];
+        double sgy = gl.x * yv.x;
+        sgy += gl.y * yv.y;
+        sgy = wave_allreduce_sum(sgy);
+        if (lane == 0) gpart[(l * nb + blk) * (NP + 1)] = sgy;
+    }
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+        if (e == 1 && !two) break;  // (uniform)
+        double* out = gpart + ((2 * p + e) * nb + blk) * (NP + 1);
+#pragma unroll
+        for (int k = 0; k < NPW; ++k) {
+            const int j = wave + 4 * k;
+            double sv = pv[k].x * gi[e].x;
+            sv += pv[k].y * gi[e].y;
+            sv = wave_allreduce_sum(sv);
+            if (lane == 0 && j < NP) out[1 + j] = sv;
+        }
+    }
+}
+
 // The same for a symmetric row shard: k_group_reduce<0> yields the shard's PARTIAL y_l, the owner's ONE all-reduce of
 // the G vectors completes them, and the dot products follow from the complete vectors (every rank computes the same).
 // gpart as above; lane pairs and wave sums as in symv_reduce_block's dot section.

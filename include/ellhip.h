@@ -268,6 +268,14 @@ int ellhip_set_shard_symmetric(ellhip_space *s, int flag);
  *                                                    that group's product pass are ONE pass over the lower triangle
  *                                                    (12 n^2 bytes instead of 16 n^2); profiled as apply_gemv.  Identical
  *                                                    bits to 0 (two passes)
+ *   ELLHIP_OPT_PACKED_OPERANDS   0 / 1      1        Ell, the matrix-core groups of ellhip_queue_run_fused, unsharded: the
+ *                                                    product passes and the fused apply + product pass fetch the group's
+ *                                                    gradients and the recorded vectors from copies laid out in MFMA operand
+ *                                                    order, and store the column partial sums of two cuts side by side:
+ *                                                    16 bytes per lane and instruction instead of 8 (fewer vector-memory
+ *                                                    instructions beside the f64 MFMAs).  Every MFMA receives the operands
+ *                                                    it received before, every sum is added in the same order: identical
+ *                                                    bits to 0.  Read when a queue run starts; row shards always run as 0
  *   ELLHIP_OPT_STABLE_SOLVE      0 .. 3     3        EllStable: 0 = one launch per 128-block (no in-launch waits),
  *                                                    1 = persistent solves, 2 = persistent + helper workgroups,
  *                                                    3 = 2 on the MIRRORED layout: the handle's private buffer holds the
@@ -313,6 +321,7 @@ int ellhip_set_shard_symmetric(ellhip_space *s, int flag);
                                            writes each gradient straight into (fine-grained) device memory instead of into a
                                            pinned buffer a kernel then pulls over PCIe */
 #define ELLHIP_OPT_APPLY_SYMM 21
+#define ELLHIP_OPT_PACKED_OPERANDS 22
 int ellhip_set_option(ellhip_space *s, int key, int64_t value);
 int ellhip_get_option(const ellhip_space *s, int key, int64_t *value);
 int ellhip_set_default_option(int key, int64_t value);
