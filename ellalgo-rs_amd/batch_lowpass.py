@@ -1,0 +1,112 @@
+"""Python mirror of the batched device-resident low-pass filter design loop (include/ellhip_batch_lowpass.h): B
+independent `LowpassOracle`s (src/oracles/lowpass_oracle.rs) of one filter length n <= 128, each with its own band edges,
+ripple limits and round-robin cursors and its own ellipsoid of an `EllBatch`, over one shared 15n x n table; solved by one
+kernel per chunk of iterations.  Bit-identical to the CPU arithmetic."""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import capi
+from .ell import _f64, _p
+
+STATE_INTS = ("more_alt", "idx1", "idx2", "idx3", "kmax", "nwpass", "nwstop")
+STATE_DOUBLES = ("fmax", "sp_sq")
+
+
+class BatchLowpassProblem:
+    def __init__(self, n: int, wpass, wstop, lp_sq, up_sq, sp_sq, spectrum=None, *, device: int = -1):
+        """wpass, wstop, lp_sq, up_sq, sp_sq: [B] each (scalars are broadcast to the longest); spectrum: the shared
+        (15 n) x n table or None to have it computed as the reference does."""
+        self._lib = capi.load()
+        arrs = [np.atleast_1d(np.asarray(a, dtype=np.float64)) for a in (wpass, wstop, lp_sq, up_sq, sp_sq)]
+        B = max(a.size for a in arrs)
+        arrs = [np.ascontiguousarray(np.broadcast_to(a, (B,))) for a in arrs]
+        n = int(n)
+        spectrum = None if spectrum is None else _f64(spectrum, 15 * n * n)
+        h = C.c_void_p()
+        capi.check(self._lib.ellhip_batch_lowpass_create(C.byref(h), B, n, *[_p(a) for a in arrs], _p(spectrum), device),
+                   "ellhip_batch_lowpass_create")
+        self._h = h
+        self.B, self.n = int(B), n
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            self._lib.ellhip_batch_lowpass_destroy(h)
+
+    @property
+    def spectrum(self):
+        out = np.empty((15 * self.n, self.n))
+        capi.check(self._lib.ellhip_batch_lowpass_get_spectrum(self._h, _p(out)), "ellhip_batch_lowpass_get_spectrum")
+        return out
+
+    def state(self):
+        """dict of [B] arrays: more_alt, idx1, idx2, idx3, kmax, nwpass, nwstop (int32), fmax, sp_sq (float64)"""
+        ints = np.empty((self.B, 7), dtype=np.int32)
+        dbls = np.empty((self.B, 2))
+        capi.check(self._lib.ellhip_batch_lowpass_state(self._h, _p(ints), _p(dbls)), "ellhip_batch_lowpass_state")
+        out = {k: ints[:, j].copy() for j, k in enumerate(STATE_INTS)}
+        out.update({k: dbls[:, j].copy() for j, k in enumerate(STATE_DOUBLES)})
+        return out
+
+    def reset(self):
+        """cursors, fmax and kmax as after new()"""
+        capi.check(self._lib.ellhip_batch_lowpass_reset(self._h), "ellhip_batch_lowpass_reset")
+
+    def set_chunk(self, iters: int):
+        capi.check(self._lib.ellhip_batch_lowpass_set_chunk(self._h, int(iters)), "ellhip_batch_lowpass_set_chunk")
+
+    def assess_feas(self, x):
+        """One assess_feas per problem.  Returns (grad [B][n], beta0 [B], has_beta1 [B], beta1 [B], cut [B]); rows of
+        problems without a cut (cut[b] == 0) are NaN / 0."""
+        x = _f64(x, self.B * self.n)
+        grad = np.full((self.B, self.n), np.nan)
+        beta0 = np.full(self.B, np.nan)
+        beta1 = np.full(self.B, np.nan)
+        has1 = np.zeros(self.B, dtype=np.int32)
+        cut = np.empty(self.B, dtype=np.int32)
+        capi.check(self._lib.ellhip_batch_lowpass_assess_feas(self._h, _p(x), _p(grad), _p(beta0), _p(has1), _p(beta1),
+                                                              _p(cut)), "ellhip_batch_lowpass_assess_feas")
+        return grad, beta0, has1, beta1, cut
+
+    def assess_optim(self, x, gamma):
+        """One assess_optim per problem.  Returns (grad, beta0, has_beta1, beta1, shrunk [B], gamma [B], rc [B]); rc[b] is
+        1, or capi.E_STATE where the reference would panic (that problem's rows are NaN / 0, its gamma unchanged)."""
+        x = _f64(x, self.B * self.n)
+        gamma = np.array(np.broadcast_to(np.asarray(gamma, dtype=np.float64), (self.B,)))
+        grad = np.full((self.B, self.n), np.nan)
+        beta0 = np.full(self.B, np.nan)
+        beta1 = np.full(self.B, np.nan)
+        has1 = np.zeros(self.B, dtype=np.int32)
+        shrunk = np.empty(self.B, dtype=np.int32)
+        rc = np.empty(self.B, dtype=np.int32)
+        capi.check(self._lib.ellhip_batch_lowpass_assess_optim(self._h, _p(x), _p(gamma), _p(grad), _p(beta0), _p(has1),
+                                                               _p(beta1), _p(shrunk), _p(rc)),
+                   "ellhip_batch_lowpass_assess_optim")
+        return grad, beta0, has1, beta1, shrunk, gamma, rc
+
+    def optim(self, batch, gamma, max_iters: int, tol: float):
+        """cutting_plane_optim per problem on `batch` (an EllBatch).  Returns (x_best [B][n] with NaN rows where there is
+        none, has_best [B], niter [B], gamma [B], status [B])."""
+        gamma = np.array(np.broadcast_to(np.asarray(gamma, dtype=np.float64), (self.B,)))
+        x_best = np.full((self.B, self.n), np.nan)
+        has = np.empty(self.B, dtype=np.int32)
+        niter = np.empty(self.B, dtype=np.int64)
+        status = np.empty(self.B, dtype=np.int32)
+        capi.check(self._lib.ellhip_batch_lowpass_optim(batch._h, self._h, _p(gamma), int(max_iters), float(tol),
+                                                        _p(x_best), _p(has), _p(niter), _p(status)),
+                   "ellhip_batch_lowpass_optim")
+        return x_best, has, niter, gamma, status
+
+    def feas(self, batch, max_iters: int, tol: float):
+        """cutting_plane_feas per problem.  Returns (x [B][n] with NaN rows where none was found, feasible [B], niter [B],
+        status [B])."""
+        x = np.full((self.B, self.n), np.nan)
+        ok = np.empty(self.B, dtype=np.int32)
+        niter = np.empty(self.B, dtype=np.int64)
+        status = np.empty(self.B, dtype=np.int32)
+        capi.check(self._lib.ellhip_batch_lowpass_feas(batch._h, self._h, int(max_iters), float(tol), _p(x), _p(ok),
+                                                       _p(niter), _p(status)), "ellhip_batch_lowpass_feas")
+        return x, ok, niter, status

@@ -69,6 +69,14 @@ BATCH_LMI_EXPORTS = [
     "ellhip_batch_lmi_set_idx", "ellhip_batch_lmi_optim", "ellhip_batch_lmi_feas", "ellhip_batch_lmi_set_chunk",
 ]
 
+# every symbol include/ellhip_batch_lowpass.h declares (kept apart from EXPORTS, like SVM_EXPORTS)
+BATCH_LOWPASS_EXPORTS = [
+    "ellhip_batch_lowpass_create", "ellhip_batch_lowpass_destroy", "ellhip_batch_lowpass_assess_feas",
+    "ellhip_batch_lowpass_assess_optim", "ellhip_batch_lowpass_state", "ellhip_batch_lowpass_reset",
+    "ellhip_batch_lowpass_get_spectrum", "ellhip_batch_lowpass_optim", "ellhip_batch_lowpass_feas",
+    "ellhip_batch_lowpass_set_chunk",
+]
+
 
 class EllHipError(RuntimeError):
     pass
@@ -278,8 +286,19 @@ def load():
         "ellhip_batch_lmi_optim": (i32, [vp, vp, vp, i64, dbl, vp, vp, vp, vp]),
         "ellhip_batch_lmi_feas": (i32, [vp, vp, i64, dbl, vp, vp, vp, vp]),
         "ellhip_batch_lmi_set_chunk": (i32, [vp, i64]),
+        # include/ellhip_batch_lowpass.h
+        "ellhip_batch_lowpass_create": (i32, [C.POINTER(vp), i64, i64, vp, vp, vp, vp, vp, vp, i32]),
+        "ellhip_batch_lowpass_destroy": (None, [vp]),
+        "ellhip_batch_lowpass_assess_feas": (i32, [vp, vp, vp, vp, vp, vp, vp]),
+        "ellhip_batch_lowpass_assess_optim": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "ellhip_batch_lowpass_state": (i32, [vp, vp, vp]),
+        "ellhip_batch_lowpass_reset": (i32, [vp]),
+        "ellhip_batch_lowpass_get_spectrum": (i32, [vp, vp]),
+        "ellhip_batch_lowpass_optim": (i32, [vp, vp, vp, i64, dbl, vp, vp, vp, vp]),
+        "ellhip_batch_lowpass_feas": (i32, [vp, vp, i64, dbl, vp, vp, vp, vp]),
+        "ellhip_batch_lowpass_set_chunk": (i32, [vp, i64]),
     }
-    for name in EXPORTS + SVM_EXPORTS + BATCH_LMI_EXPORTS:
+    for name in EXPORTS + SVM_EXPORTS + BATCH_LMI_EXPORTS + BATCH_LOWPASS_EXPORTS:
         fn = getattr(L, name)  # AttributeError if the library does not export it
         fn.restype, fn.argtypes = sig[name]
     _lib = L

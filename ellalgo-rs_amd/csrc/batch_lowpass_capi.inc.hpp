@@ -1,0 +1,382 @@
+// batch_lowpass_capi.inc.hpp -- C ABI of the batched device-resident low-pass filter design loop
+// (include/ellhip_batch_lowpass.h).  Included at the end of ellhip_capi.hip, after lowpass_capi.inc.hpp (it builds the
+// table with the same lp_fill_rows), batch_capi.inc.hpp (it drives the batch engine's handle directly) and
+// batch_lmi_capi.inc.hpp (batch_lmi_allow_lds).
+//
+// Reference: src/oracles/lowpass_oracle.rs:22-151 (oracle), src/cutting_plane.rs:205-227, 286-313 (loops).
+#include "../../include/ellhip_batch_lowpass.h"
+
+#include "batch_lowpass_kernels.hpp"
+
+struct ellhip_batch_lowpass {
+    int device = 0;
+    long long B = 0;
+    int n = 0;
+    int mdim = 0;
+    int chunk = 256;
+    std::vector<int> bands;       // host copy of [B][2]: nwpass, nwstop (reset, state)
+    double* d_spec = nullptr;     // [15 n][n]
+    double* d_specT = nullptr;    // [n][15 n]
+    int* d_bands = nullptr;       // [B][2]
+    double* d_lims = nullptr;     // [B][2]: lp_sq, up_sq
+    int* d_cursor = nullptr;      // [B][4]: idx1, idx2, idx3, more_alt
+    int* d_kmax = nullptr;        // [B]
+    double* d_fmax = nullptr;     // [B]
+    double* d_spsq = nullptr;     // [B]
+    double* d_gamma = nullptr;    // [B]
+    double* d_xbest = nullptr;    // [B][n]
+    long long* d_niter = nullptr; // [B]
+    int* d_ints = nullptr;        // has_best [B], stopped [B], status [B], nstopped [1]
+    double* d_x = nullptr;        // assess: [B][n]
+    double* d_grad = nullptr;     // assess: [B][n]
+    double* d_beta = nullptr;     // assess: beta0 [B], beta1 [B]
+    int* d_aints = nullptr;       // assess: has_beta1 [B], answer [B]
+    hipStream_t stream = nullptr;
+};
+
+namespace {
+
+BatchLpArrays batch_lowpass_arrays(ellhip_batch_lowpass* o) {
+    const size_t B = (size_t)o->B;
+    BatchLpArrays A;
+    A.spec = o->d_spec;
+    A.specT = o->d_specT;
+    A.bands = o->d_bands;
+    A.lims = o->d_lims;
+    A.cursor = o->d_cursor;
+    A.kmax = o->d_kmax;
+    A.fmax = o->d_fmax;
+    A.spsq = o->d_spsq;
+    A.gamma = o->d_gamma;
+    A.xbest = o->d_xbest;
+    A.has_best = o->d_ints;
+    A.niter = o->d_niter;
+    A.stopped = o->d_ints + B;
+    A.status = o->d_ints + 2 * B;
+    A.nstopped = o->d_ints + 3 * B;
+    return A;
+}
+
+// cursors, fmax and kmax as LowpassOracle::new leaves them (src/oracles/lowpass_oracle.rs:41-52)
+int batch_lowpass_fresh(ellhip_batch_lowpass* o) {
+    const size_t B = (size_t)o->B;
+    std::vector<int> cur(4 * B), kmax(B, -1);
+    std::vector<double> fmax(B, -__builtin_inf());
+    for (size_t b = 0; b < B; ++b) {
+        cur[4 * b] = -1;
+        cur[4 * b + 1] = o->bands[2 * b] - 1;
+        cur[4 * b + 2] = o->bands[2 * b + 1] - 1;
+        cur[4 * b + 3] = 1;
+    }
+    HIPCHK(hipMemcpy(o->d_cursor, cur.data(), 4 * B * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(o->d_kmax, kmax.data(), B * sizeof(int), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(o->d_fmax, fmax.data(), B * sizeof(double), hipMemcpyHostToDevice));
+    return 0;
+}
+
+int batch_lowpass_run(ellhip_batch* s, ellhip_batch_lowpass* o, int feas, double* gamma_inout, int64_t max_iters,
+                      double tol, double* x_out, int32_t* has_out, int64_t* niter_out, int32_t* status_out) {
+    if (!s || !o || !has_out || !niter_out || !status_out || (!feas && !gamma_inout))
+        return fail(ELLHIP_E_INVALID, "NULL argument");
+    if (s->variant != ELLHIP_SPACE_ELL)
+        return fail(ELLHIP_E_INVALID, "batched lowpass loop: EllStable batch handles are not supported");
+    if (s->B != o->B || s->n != o->n)
+        return fail(ELLHIP_E_INVALID, "batched lowpass loop: spaces and oracle differ in B or n");
+    if (s->device != o->device)
+        return fail(ELLHIP_E_INVALID, "batched lowpass loop: spaces and oracle live on different devices");
+    if (max_iters < 0) return fail(ELLHIP_E_INVALID, "max_iters must be >= 0");
+    const size_t B = (size_t)o->B, n = (size_t)o->n;
+    const size_t lds = (size_t)s->epw * (batch_lds_doubles(s->n) + batch_lowpass_lds_doubles(s->n)) * sizeof(double);
+    if (lds > BATCH_LMI_LDS_MAX) return fail(ELLHIP_E_INVALID, "batched lowpass loop: this n needs more LDS than a workgroup has");
+    DeviceGuard guard(s->device);
+    BatchLpArrays A = batch_lowpass_arrays(o);
+    HIPCHK(hipStreamSynchronize(s->stream));
+    HIPCHK(hipStreamSynchronize(o->stream));
+    HIPCHK(fill_now(o->d_ints, 0, (3 * B + 1) * sizeof(int), s->stream));
+    HIPCHK(fill_now(o->d_niter, 0, B * sizeof(long long), s->stream));
+    if (!feas) HIPCHK(hipMemcpy(o->d_gamma, gamma_inout, B * sizeof(double), hipMemcpyHostToDevice));
+    BatchParams P;
+    P.B = s->B;
+    P.n = s->n;
+    P.pitch = batch_pitch(s->n);
+    P.epw = s->epw;
+    P.K = 0;
+    P.no_defer_trick = s->no_defer_trick;
+    const unsigned grid = (unsigned)((s->B + s->epw - 1) / s->epw);
+    const EllCalcDev calc = EllCalcDev::make(s->n, s->use_parallel_cut);
+    BatchLpLoop R;
+    R.feas = feas;
+    R.mdim = o->mdim;
+    R.max_iters = max_iters;
+    R.tol = tol;
+    for (long long done = 0; done < max_iters; done += o->chunk) {
+        R.iters = (int)std::min<long long>(o->chunk, max_iters - done);
+#define BATCH_LP_GO(TT, SLOT)                                                                                         \
+    do {                                                                                                              \
+        const int rc_ = batch_lmi_allow_lds(&k_batch_lowpass_loop<TT>, s->device, SLOT, lds);                         \
+        if (rc_) return rc_;                                                                                          \
+        hipLaunchKernelGGL(k_batch_lowpass_loop<TT>, dim3(grid), dim3(TT), lds, s->stream, P, R, s->d_Q, s->d_xc,     \
+                           s->d_kappa, s->d_tsq, A, calc);                                                            \
+    } while (0)
+        if (s->T == 64) BATCH_LP_GO(64, 0);
+        else if (s->T == 128) BATCH_LP_GO(128, 1);
+        else BATCH_LP_GO(256, 2);
+#undef BATCH_LP_GO
+        HIPCHK(hipGetLastError());
+        int nstopped = 0;
+        HIPCHK(hipMemcpyAsync(&nstopped, A.nstopped, sizeof(int), hipMemcpyDeviceToHost, s->stream));
+        HIPCHK(hipStreamSynchronize(s->stream));
+        if ((long long)nstopped >= o->B) break;
+    }
+    std::vector<int32_t> has(B);
+    std::vector<long long> niter(B);
+    HIPCHK(hipMemcpy(has.data(), A.has_best, B * sizeof(int), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(status_out, A.status, B * sizeof(int), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(niter.data(), o->d_niter, B * sizeof(long long), hipMemcpyDeviceToHost));
+    if (!feas) HIPCHK(hipMemcpy(gamma_inout, o->d_gamma, B * sizeof(double), hipMemcpyDeviceToHost));
+    for (size_t b = 0; b < B; ++b) {
+        has_out[b] = has[b];
+        niter_out[b] = niter[b];
+    }
+    if (x_out) {
+        std::vector<double> xb(B * n);
+        HIPCHK(hipMemcpy(xb.data(), o->d_xbest, B * n * sizeof(double), hipMemcpyDeviceToHost));
+        for (size_t b = 0; b < B; ++b)
+            if (has[b]) memcpy(x_out + b * n, xb.data() + b * n, n * sizeof(double));
+    }
+    return 0;
+}
+
+// one oracle call per problem; ans[B] = BLP_*
+int batch_lowpass_assess(ellhip_batch_lowpass* o, int optim, const double* x, double* gamma_inout, double* grad_out,
+                         double* beta0, int32_t* has_beta1, double* beta1, std::vector<int>& ans) {
+    if (!o || !x || !grad_out || !beta0 || !has_beta1 || !beta1 || (optim && !gamma_inout))
+        return fail(ELLHIP_E_INVALID, "NULL argument");
+    DeviceGuard guard(o->device);
+    const size_t B = (size_t)o->B, n = (size_t)o->n;
+    const int T = o->n <= 64 ? 256 : 128;
+    const int epw = std::min(64, T / o->n);
+    const size_t lds = (size_t)epw * (batch_lowpass_lds_doubles(o->n) + n) * sizeof(double);  // at most 64 * 29 * 8 bytes
+    const unsigned grid = (unsigned)((o->B + epw - 1) / epw);
+    double* d_beta0 = o->d_beta;
+    double* d_beta1 = o->d_beta + B;
+    int* d_hb1 = o->d_aints;
+    int* d_ans = o->d_aints + B;
+    BatchLpArrays A = batch_lowpass_arrays(o);
+    HIPCHK(hipMemcpy(o->d_x, x, B * n * sizeof(double), hipMemcpyHostToDevice));
+    if (optim) HIPCHK(hipMemcpy(o->d_gamma, gamma_inout, B * sizeof(double), hipMemcpyHostToDevice));
+#define BATCH_LP_ASSESS(TT)                                                                                            \
+    hipLaunchKernelGGL(k_batch_lowpass_assess<TT>, dim3(grid), dim3(TT), lds, o->stream, o->B, o->n, epw, o->mdim,     \
+                       optim, A, (const double*)o->d_x, o->d_grad, d_beta0, d_hb1, d_beta1, d_ans)
+    if (T == 128) BATCH_LP_ASSESS(128);
+    else BATCH_LP_ASSESS(256);
+#undef BATCH_LP_ASSESS
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(o->stream));
+    std::vector<double> g(B * n), b0(B), b1(B);
+    std::vector<int> hb1(B);
+    ans.resize(B);
+    HIPCHK(hipMemcpy(ans.data(), d_ans, B * sizeof(int), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(g.data(), o->d_grad, B * n * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(b0.data(), d_beta0, B * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(b1.data(), d_beta1, B * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(hb1.data(), d_hb1, B * sizeof(int), hipMemcpyDeviceToHost));
+    if (optim) HIPCHK(hipMemcpy(gamma_inout, o->d_gamma, B * sizeof(double), hipMemcpyDeviceToHost));
+    for (size_t b = 0; b < B; ++b) {  // a problem without a cut leaves its outputs as the caller had them
+        if (ans[b] != BLP_CUT && ans[b] != BLP_SHRUNK) continue;
+        memcpy(grad_out + b * n, g.data() + b * n, n * sizeof(double));
+        beta0[b] = b0[b];
+        has_beta1[b] = hb1[b];
+        beta1[b] = b1[b];
+    }
+    return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ellhip_batch_lowpass_create(ellhip_batch_lowpass** out, int64_t B, int64_t n, const double* wpass, const double* wstop,
+                                const double* lp_sq, const double* up_sq, const double* sp_sq, const double* spectrum,
+                                int device) {
+    if (!out) return fail(ELLHIP_E_INVALID, "out is NULL");
+    *out = nullptr;
+    if (B < 1 || n < 1 || n > BATCH_NMAX) return fail(ELLHIP_E_INVALID, "batched lowpass: need B >= 1 and 1 <= n <= 128");
+    if (B > (1 << 24)) return fail(ELLHIP_E_INVALID, "batched lowpass: B too large");
+    if (!wpass || !wstop || !lp_sq || !up_sq || !sp_sq) return fail(ELLHIP_E_INVALID, "NULL argument");
+    const long long mdim = 15 * n;  //                                      src/oracles/lowpass_oracle.rs:24
+    const size_t sB = (size_t)B, sn = (size_t)n;
+    std::vector<int> bands(2 * sB);
+    std::vector<double> lims(2 * sB);
+    for (size_t b = 0; b < sB; ++b) {
+        if (wpass[b] > wstop[b]) return fail(ELLHIP_E_INVALID, "batched lowpass: wpass > wstop");
+        const double fpass = std::floor(wpass[b] * (double)(mdim - 1));  //   :36
+        const double fstop = std::floor(wstop[b] * (double)(mdim - 1));  //   :37
+        if (!(fpass >= 0.0 && fpass <= fstop && fstop <= (double)(mdim - 1)))  // (NaN fails too)
+            return fail(ELLHIP_E_INVALID, "batched lowpass: band edges must satisfy 0 <= wpass <= wstop <= 1");
+        const long long nwpass = (long long)fpass + 1, nwstop = (long long)fstop + 1;
+        bands[2 * b] = (int)nwpass;
+        bands[2 * b + 1] = (int)nwstop;
+        lims[2 * b] = lp_sq[b];
+        lims[2 * b + 1] = up_sq[b];
+    }
+    const int ndev = ellhip_device_count();
+    if (ndev <= 0) return fail(ELLHIP_E_NODEVICE, "no HIP device: the batched lowpass loop has no CPU path");
+    if (device < 0 && hipGetDevice(&device) != hipSuccess) device = 0;
+    if (device >= ndev) return fail(ELLHIP_E_INVALID, "device index out of range");
+    ellhip_batch_lowpass* o = new (std::nothrow) ellhip_batch_lowpass();
+    if (!o) return fail(ELLHIP_E_NOMEM, "host allocation failed");
+    o->device = device;
+    o->B = B;
+    o->n = (int)n;
+    o->mdim = (int)mdim;
+    o->bands = bands;
+    DeviceGuard guard(device);
+    auto bail = [&](int code) {
+        ellhip_batch_lowpass_destroy(o);
+        return code;
+    };
+    // the table: the caller's own or computed with the host libm exactly as LowpassOracle::new does (:25-34), and its
+    // transpose
+    const size_t tab = (size_t)mdim * sn;
+    std::vector<double> rows(tab), cols(tab);
+    if (spectrum) memcpy(rows.data(), spectrum, tab * sizeof(double));
+    else lp_fill_rows(rows.data(), (long long)n, mdim, 0, mdim);
+    for (size_t r = 0; r < (size_t)mdim; ++r)
+        for (size_t j = 0; j < sn; ++j) cols[j * (size_t)mdim + r] = rows[r * sn + j];
+    hipError_t e = hipStreamCreateWithFlags(&o->stream, hipStreamNonBlocking);
+    if (e == hipSuccess) e = hipMalloc(&o->d_spec, tab * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc(&o->d_specT, tab * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc(&o->d_bands, 2 * sB * sizeof(int));
+    if (e == hipSuccess) e = hipMalloc(&o->d_lims, 2 * sB * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc(&o->d_cursor, 4 * sB * sizeof(int));
+    if (e == hipSuccess) e = hipMalloc(&o->d_kmax, sB * sizeof(int));
+    if (e == hipSuccess) e = hipMalloc(&o->d_fmax, sB * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc(&o->d_spsq, sB * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc(&o->d_gamma, sB * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc(&o->d_xbest, sB * sn * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc(&o->d_niter, sB * sizeof(long long));
+    if (e == hipSuccess) e = hipMalloc(&o->d_ints, (3 * sB + 1) * sizeof(int));
+    if (e == hipSuccess) e = hipMalloc(&o->d_x, sB * sn * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc(&o->d_grad, sB * sn * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc(&o->d_beta, 2 * sB * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc(&o->d_aints, 2 * sB * sizeof(int));
+    if (e != hipSuccess)
+        return bail(fail(e == hipErrorOutOfMemory ? ELLHIP_E_NOMEM : ELLHIP_E_HIP, "batched lowpass allocation", e));
+    e = hipMemcpy(o->d_spec, rows.data(), tab * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(o->d_specT, cols.data(), tab * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(o->d_bands, bands.data(), 2 * sB * sizeof(int), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(o->d_lims, lims.data(), 2 * sB * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(o->d_spsq, sp_sq, sB * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(o->d_gamma, sp_sq, sB * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = fill_now(o->d_xbest, 0, sB * sn * sizeof(double), o->stream);
+    if (e == hipSuccess) e = fill_now(o->d_grad, 0, sB * sn * sizeof(double), o->stream);
+    if (e == hipSuccess) e = fill_now(o->d_ints, 0, (3 * sB + 1) * sizeof(int), o->stream);
+    if (e != hipSuccess) return bail(fail(ELLHIP_E_HIP, "batched lowpass upload", e));
+    const int rc = batch_lowpass_fresh(o);
+    if (rc) return bail(rc);
+    *out = o;
+    return 0;
+}
+
+void ellhip_batch_lowpass_destroy(ellhip_batch_lowpass* o) {
+    if (!o) return;
+    DeviceGuard guard(o->device);
+    if (o->stream) (void)hipStreamSynchronize(o->stream);
+    void* bufs[] = {o->d_spec,  o->d_specT, o->d_bands, o->d_lims, o->d_cursor, o->d_kmax, o->d_fmax, o->d_spsq,
+                    o->d_gamma, o->d_xbest, o->d_niter, o->d_ints, o->d_x,      o->d_grad, o->d_beta, o->d_aints};
+    for (void* p : bufs)
+        if (p) (void)hipFree(p);
+    if (o->stream) (void)hipStreamDestroy(o->stream);
+    delete o;
+}
+
+int ellhip_batch_lowpass_assess_feas(ellhip_batch_lowpass* o, const double* x, double* grad_out, double* beta0,
+                                     int32_t* has_beta1, double* beta1, int32_t* cut_out) {
+    if (!cut_out) return fail(ELLHIP_E_INVALID, "NULL argument");
+    std::vector<int> ans;
+    const int rc = batch_lowpass_assess(o, 0, x, nullptr, grad_out, beta0, has_beta1, beta1, ans);
+    if (rc) return rc;
+    for (size_t b = 0; b < ans.size(); ++b) cut_out[b] = ans[b] == BLP_CUT ? 1 : 0;
+    return 0;
+}
+
+int ellhip_batch_lowpass_assess_optim(ellhip_batch_lowpass* o, const double* x, double* gamma_inout, double* grad_out,
+                                      double* beta0, int32_t* has_beta1, double* beta1, int32_t* shrunk_out,
+                                      int32_t* rc_out) {
+    if (!shrunk_out || !rc_out) return fail(ELLHIP_E_INVALID, "NULL argument");
+    std::vector<int> ans;
+    const int rc = batch_lowpass_assess(o, 1, x, gamma_inout, grad_out, beta0, has_beta1, beta1, ans);
+    if (rc) return rc;
+    for (size_t b = 0; b < ans.size(); ++b) {
+        shrunk_out[b] = ans[b] == BLP_SHRUNK ? 1 : 0;
+        rc_out[b] = (ans[b] == BLP_CUT || ans[b] == BLP_SHRUNK) ? 1 : ELLHIP_E_STATE;
+    }
+    return 0;
+}
+
+int ellhip_batch_lowpass_state(ellhip_batch_lowpass* o, int32_t* ints7, double* doubles2) {
+    if (!o) return fail(ELLHIP_E_INVALID, "NULL handle");
+    DeviceGuard guard(o->device);
+    HIPCHK(hipStreamSynchronize(o->stream));
+    const size_t B = (size_t)o->B;
+    if (ints7) {
+        std::vector<int> cur(4 * B), kmax(B);
+        HIPCHK(hipMemcpy(cur.data(), o->d_cursor, 4 * B * sizeof(int), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(kmax.data(), o->d_kmax, B * sizeof(int), hipMemcpyDeviceToHost));
+        for (size_t b = 0; b < B; ++b) {
+            int32_t* r = ints7 + 7 * b;
+            r[0] = cur[4 * b + 3];
+            r[1] = cur[4 * b];
+            r[2] = cur[4 * b + 1];
+            r[3] = cur[4 * b + 2];
+            r[4] = kmax[b];
+            r[5] = o->bands[2 * b];
+            r[6] = o->bands[2 * b + 1];
+        }
+    }
+    if (doubles2) {
+        std::vector<double> fmax(B), spsq(B);
+        HIPCHK(hipMemcpy(fmax.data(), o->d_fmax, B * sizeof(double), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(spsq.data(), o->d_spsq, B * sizeof(double), hipMemcpyDeviceToHost));
+        for (size_t b = 0; b < B; ++b) {
+            doubles2[2 * b] = fmax[b];
+            doubles2[2 * b + 1] = spsq[b];
+        }
+    }
+    return 0;
+}
+
+int ellhip_batch_lowpass_reset(ellhip_batch_lowpass* o) {
+    if (!o) return fail(ELLHIP_E_INVALID, "NULL handle");
+    DeviceGuard guard(o->device);
+    HIPCHK(hipStreamSynchronize(o->stream));
+    return batch_lowpass_fresh(o);
+}
+
+int ellhip_batch_lowpass_get_spectrum(ellhip_batch_lowpass* o, double* out) {
+    if (!o || !out) return fail(ELLHIP_E_INVALID, "NULL argument");
+    DeviceGuard guard(o->device);
+    HIPCHK(hipMemcpy(out, o->d_spec, (size_t)o->mdim * (size_t)o->n * sizeof(double), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+int ellhip_batch_lowpass_optim(ellhip_batch* spaces, ellhip_batch_lowpass* o, double* gamma_inout, int64_t max_iters,
+                               double tol, double* x_best_out, int32_t* has_best_out, int64_t* niter_out,
+                               int32_t* status_out) {
+    return batch_lowpass_run(spaces, o, 0, gamma_inout, max_iters, tol, x_best_out, has_best_out, niter_out, status_out);
+}
+
+int ellhip_batch_lowpass_feas(ellhip_batch* spaces, ellhip_batch_lowpass* o, int64_t max_iters, double tol, double* x_out,
+                              int32_t* feasible_out, int64_t* niter_out, int32_t* status_out) {
+    return batch_lowpass_run(spaces, o, 1, nullptr, max_iters, tol, x_out, feasible_out, niter_out, status_out);
+}
+
+int ellhip_batch_lowpass_set_chunk(ellhip_batch_lowpass* o, int64_t iters) {
+    if (!o) return fail(ELLHIP_E_INVALID, "NULL handle");
+    if (iters < 1 || iters > 4096) return fail(ELLHIP_E_INVALID, "batched lowpass: chunk must be in 1..4096");
+    o->chunk = (int)iters;
+    return 0;
+}
+
+}  // extern "C"

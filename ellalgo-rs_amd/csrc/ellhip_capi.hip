@@ -3038,3 +3038,4 @@ int ellhip_profile_read(ellhip_space* s, double* ms_out, int64_t* count_out) {
 #include "sharded_capi.inc.hpp"
 #include "svm_capi.inc.hpp"
 #include "batch_lmi_capi.inc.hpp"
+#include "batch_lowpass_capi.inc.hpp"
