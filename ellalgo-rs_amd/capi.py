@@ -77,6 +77,12 @@ BATCH_LOWPASS_EXPORTS = [
     "ellhip_batch_lowpass_set_chunk",
 ]
 
+# every symbol include/ellhip_batch_svm.h declares (kept apart from EXPORTS, like SVM_EXPORTS)
+BATCH_SVM_EXPORTS = [
+    "ellhip_batch_svm_create", "ellhip_batch_svm_destroy", "ellhip_batch_svm_margins", "ellhip_batch_svm_assess_optim",
+    "ellhip_batch_svm_last", "ellhip_batch_svm_optim", "ellhip_batch_svm_set_chunk",
+]
+
 
 class EllHipError(RuntimeError):
     pass
@@ -297,8 +303,16 @@ def load():
         "ellhip_batch_lowpass_optim": (i32, [vp, vp, vp, i64, dbl, vp, vp, vp, vp]),
         "ellhip_batch_lowpass_feas": (i32, [vp, vp, i64, dbl, vp, vp, vp, vp]),
         "ellhip_batch_lowpass_set_chunk": (i32, [vp, i64]),
+        # include/ellhip_batch_svm.h
+        "ellhip_batch_svm_create": (i32, [C.POINTER(vp), i64, i64, i64, vp, i32, vp, i32]),
+        "ellhip_batch_svm_destroy": (None, [vp]),
+        "ellhip_batch_svm_margins": (i32, [vp, vp, vp]),
+        "ellhip_batch_svm_assess_optim": (i32, [vp, vp, vp, vp, vp]),
+        "ellhip_batch_svm_last": (i32, [vp, vp, vp]),
+        "ellhip_batch_svm_optim": (i32, [vp, vp, vp, i64, dbl, vp, vp, vp, vp]),
+        "ellhip_batch_svm_set_chunk": (i32, [vp, i64]),
     }
-    for name in EXPORTS + SVM_EXPORTS + BATCH_LMI_EXPORTS + BATCH_LOWPASS_EXPORTS:
+    for name in EXPORTS + SVM_EXPORTS + BATCH_LMI_EXPORTS + BATCH_LOWPASS_EXPORTS + BATCH_SVM_EXPORTS:
         fn = getattr(L, name)  # AttributeError if the library does not export it
         fn.restype, fn.argtypes = sig[name]
     _lib = L

@@ -3039,3 +3039,4 @@ int ellhip_profile_read(ellhip_space* s, double* ms_out, int64_t* count_out) {
 #include "svm_capi.inc.hpp"
 #include "batch_lmi_capi.inc.hpp"
 #include "batch_lowpass_capi.inc.hpp"
+#include "batch_svm_capi.inc.hpp"
