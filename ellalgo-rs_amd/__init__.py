@@ -11,10 +11,11 @@ from .batch_lmi import BatchLmiProblem  # noqa: F401
 from .batch_lowpass import BatchLowpassProblem  # noqa: F401
 from .batch_svm import BatchSvmProblem  # noqa: F401
 from .lmi import LDLTMgr, LMI0Oracle, LMIOracle  # noqa: F401
+from .lmi_loop import LmiLoopProblem  # noqa: F401
 from .lowpass import LowpassOracle, create_lowpass_case, lowpass_case_constants  # noqa: F401
 from .sharded_abi import ShardedEllAbi  # noqa: F401
 from .svm import SvmOracle  # noqa: F401
 
 __all__ = ["build", "capi", "synth", "CutStatus", "Ell", "EllStable", "ParallelCut", "SingleCut", "calc",
-           "EllBatch", "EllStableBatch", "BatchLmiProblem", "BatchLowpassProblem", "BatchSvmProblem", "LDLTMgr", "LMIOracle", "LMI0Oracle", "LowpassOracle", "create_lowpass_case", "lowpass_case_constants",
+           "EllBatch", "EllStableBatch", "BatchLmiProblem", "BatchLowpassProblem", "BatchSvmProblem", "LDLTMgr", "LMIOracle", "LMI0Oracle", "LmiLoopProblem", "LowpassOracle", "create_lowpass_case", "lowpass_case_constants",
            "SvmOracle"]

@@ -77,6 +77,12 @@ BATCH_LOWPASS_EXPORTS = [
     "ellhip_batch_lowpass_set_chunk",
 ]
 
+# every symbol include/ellhip_lmi_loop.h declares (kept apart from EXPORTS, like SVM_EXPORTS)
+LMI_LOOP_EXPORTS = [
+    "ellhip_lmi_loop_create", "ellhip_lmi_loop_destroy", "ellhip_lmi_loop_get_idx", "ellhip_lmi_loop_set_idx",
+    "ellhip_lmi_loop_assess_optim", "ellhip_lmi_loop_assess_feas", "ellhip_lmi_loop_optim", "ellhip_lmi_loop_feas",
+]
+
 # every symbol include/ellhip_batch_svm.h declares (kept apart from EXPORTS, like SVM_EXPORTS)
 BATCH_SVM_EXPORTS = [
     "ellhip_batch_svm_create", "ellhip_batch_svm_destroy", "ellhip_batch_svm_margins", "ellhip_batch_svm_assess_optim",
@@ -311,8 +317,17 @@ def load():
         "ellhip_batch_svm_last": (i32, [vp, vp, vp]),
         "ellhip_batch_svm_optim": (i32, [vp, vp, vp, i64, dbl, vp, vp, vp, vp]),
         "ellhip_batch_svm_set_chunk": (i32, [vp, i64]),
+        # include/ellhip_lmi_loop.h
+        "ellhip_lmi_loop_create": (i32, [C.POINTER(vp), vp, i64, vp]),
+        "ellhip_lmi_loop_destroy": (None, [vp]),
+        "ellhip_lmi_loop_get_idx": (i32, [vp, C.POINTER(i32)]),
+        "ellhip_lmi_loop_set_idx": (i32, [vp, i32]),
+        "ellhip_lmi_loop_assess_optim": (i32, [vp, vp, C.POINTER(dbl), vp, C.POINTER(dbl), C.POINTER(i32)]),
+        "ellhip_lmi_loop_assess_feas": (i32, [vp, vp, vp, C.POINTER(dbl), C.POINTER(i32)]),
+        "ellhip_lmi_loop_optim": (i32, [vp, vp, C.POINTER(dbl), i64, dbl, vp, C.POINTER(i32), C.POINTER(i64)]),
+        "ellhip_lmi_loop_feas": (i32, [vp, vp, i64, dbl, vp, C.POINTER(i32), C.POINTER(i64)]),
     }
-    for name in EXPORTS + SVM_EXPORTS + BATCH_LMI_EXPORTS + BATCH_LOWPASS_EXPORTS + BATCH_SVM_EXPORTS:
+    for name in EXPORTS + SVM_EXPORTS + BATCH_LMI_EXPORTS + BATCH_LOWPASS_EXPORTS + BATCH_SVM_EXPORTS + LMI_LOOP_EXPORTS:
         fn = getattr(L, name)  # AttributeError if the library does not export it
         fn.restype, fn.argtypes = sig[name]
     _lib = L

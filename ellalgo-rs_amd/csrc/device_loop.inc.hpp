@@ -95,6 +95,16 @@ int drive_device_loop(ellhip_space* s, Stage& stage, long long n, int device, lo
                 rc = do_commit(s, true, nullptr);
                 if (rc) return rc;
             }
+            if (hs.stop == STOP_FEASIBLE && s->variant == ELLHIP_SPACE_ELL && !deferring(s) && at > 0) {
+                // The oracle halted the loop at the top of iteration `at` (src/cutting_plane.rs:216-219), before that
+                // iteration's commit, which would have carried the shrink of the cut before it: that cut's update is
+                // complete in the reference.  Its gt is still in its slot and DevState still holds its scalars (every
+                // scalar stage since was a no-op).  (at == 0: the previous batch's closing commit has applied it.)
+                if (at >= nb) return fail(ELLHIP_E_STATE, "device loop: inconsistent iteration count");
+                s->cur = slot_of[(size_t)(at - 1)];
+                rc = do_commit(s, true, nullptr);
+                if (rc) return rc;
+            }
             HIPCHK(hipStreamSynchronize(st));
         }
         done += nb;

@@ -22,6 +22,45 @@ struct ellhip_lmi {
     bool factored = false;
 };
 
+namespace {
+
+// Every kernel of one oracle call at x_dev (n doubles on the device), enqueued on `st`: the one copy of the sequence, shared by
+// ellhip_lmi_assess_feas (st = the handle's own stream, x_dev = d_x) and by the slots of the device-resident loop
+// (lmi_loop_capi.inc.hpp: st = the search space's stream, x_dev = its centre).  Each kernel is gated on the device-side
+// LmiState, so nothing here waits for the host.
+int lmi_issue(ellhip_lmi* o, hipStream_t st, const double* x_dev) {
+    const long long m = o->m, n = o->n;
+    hipLaunchKernelGGL(k_ldlt_clear, dim3(1024), dim3(256), 0, st, o->d_S, m, o->d_st);
+    for (long long k0 = 0; k0 < m; k0 += LMI_NB) {
+        if (k0 % LMI_FORM_W == 0)
+            hipLaunchKernelGGL(k_lmi_form, dim3((unsigned)(m - k0)), dim3(LMI_FORM_W), 0, st, (const double*)o->d_F,
+                               (const double*)o->d_B, x_dev, o->d_A, m, n, k0, o->mode,
+                               (const LmiState*)o->d_st);
+        hipLaunchKernelGGL(k_ldlt_diag, dim3(1), dim3(64), 0, st, (const double*)o->d_A, o->d_S, m, k0, o->d_st);
+        const long long k1 = k0 + LMI_NB;
+        if (k1 < m) {
+            hipLaunchKernelGGL(k_ldlt_panel, dim3((unsigned)((m - k1 + 127) / 128)), dim3(128), 0, st,
+                               (const double*)o->d_A, o->d_S, m, k0, (const LmiState*)o->d_st);
+            const unsigned tiles = (unsigned)((m - k1 + 63) / 64);
+            hipLaunchKernelGGL(k_ldlt_update, dim3(tiles, tiles), dim3(256), 0, st, o->d_S, m, k0,
+                               (const LmiState*)o->d_st);
+        }
+    }
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_lmi_witness, dim3(1), dim3(1024), 0, st, (const double*)o->d_S, m, o->d_v,
+                       (const LmiState*)o->d_st);
+    if (n > 0) {
+        hipLaunchKernelGGL(k_lmi_quad, dim3((unsigned)n, LMI_QUAD_CHUNKS), dim3(256), 0, st, (const double*)o->d_F, m,
+                           (const double*)o->d_v, o->d_partial, (const LmiState*)o->d_st);
+        hipLaunchKernelGGL(k_lmi_quad_reduce, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n,
+                           (const double*)o->d_partial, o->d_g, o->mode, (const LmiState*)o->d_st);
+    }
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+}  // namespace
+
 extern "C" {
 
 void ellhip_lmi_destroy(ellhip_lmi* o) {
@@ -84,34 +123,10 @@ int ellhip_lmi_assess_feas(ellhip_lmi* o, const double* x, double* g_out, double
     if (o->n > 0 && (!x || !g_out)) return fail(ELLHIP_E_INVALID, "NULL argument");
     DeviceGuard guard(o->device);
     hipStream_t st = o->stream;
-    const long long m = o->m, n = o->n;
+    const long long n = o->n;
     if (n > 0) HIPCHK(hipMemcpyAsync(o->d_x, x, (size_t)n * sizeof(double), hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_ldlt_clear, dim3(1024), dim3(256), 0, st, o->d_S, m, o->d_st);
-    for (long long k0 = 0; k0 < m; k0 += LMI_NB) {
-        if (k0 % LMI_FORM_W == 0)
-            hipLaunchKernelGGL(k_lmi_form, dim3((unsigned)(m - k0)), dim3(LMI_FORM_W), 0, st, (const double*)o->d_F,
-                               (const double*)o->d_B, (const double*)o->d_x, o->d_A, m, n, k0, o->mode,
-                               (const LmiState*)o->d_st);
-        hipLaunchKernelGGL(k_ldlt_diag, dim3(1), dim3(64), 0, st, (const double*)o->d_A, o->d_S, m, k0, o->d_st);
-        const long long k1 = k0 + LMI_NB;
-        if (k1 < m) {
-            hipLaunchKernelGGL(k_ldlt_panel, dim3((unsigned)((m - k1 + 127) / 128)), dim3(128), 0, st,
-                               (const double*)o->d_A, o->d_S, m, k0, (const LmiState*)o->d_st);
-            const unsigned tiles = (unsigned)((m - k1 + 63) / 64);
-            hipLaunchKernelGGL(k_ldlt_update, dim3(tiles, tiles), dim3(256), 0, st, o->d_S, m, k0,
-                               (const LmiState*)o->d_st);
-        }
-    }
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(k_lmi_witness, dim3(1), dim3(1024), 0, st, (const double*)o->d_S, m, o->d_v,
-                       (const LmiState*)o->d_st);
-    if (n > 0) {
-        hipLaunchKernelGGL(k_lmi_quad, dim3((unsigned)n, LMI_QUAD_CHUNKS), dim3(256), 0, st, (const double*)o->d_F, m,
-                           (const double*)o->d_v, o->d_partial, (const LmiState*)o->d_st);
-        hipLaunchKernelGGL(k_lmi_quad_reduce, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, n,
-                           (const double*)o->d_partial, o->d_g, o->mode, (const LmiState*)o->d_st);
-    }
-    HIPCHK(hipGetLastError());
+    const int rc = lmi_issue(o, st, o->d_x);
+    if (rc) return rc;
     HIPCHK(hipMemcpyAsync(o->h_st, o->d_st, sizeof(LmiState), hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     o->factored = true;

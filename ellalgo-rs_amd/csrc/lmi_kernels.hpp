@@ -29,7 +29,8 @@ constexpr int LMI_FORM_W = 256;  // columns formed at a time (lazily: a failing 
 
 struct LmiState {
     int pos1;       // 0 while every pivot so far is > 0; else index of the failing row + 1 (pub pos.1)
-    int pad;
+    int skip;       // nonzero: every kernel of the call is a no-op and leaves the last call's results alone.  Zero at create;
+                    // only the device-resident loop's gate kernel sets it (lmi_loop_kernels.hpp), for one slot at a time
     double ep;      // -storage[pos1-1][pos1-1]
 };
 
@@ -39,7 +40,7 @@ __global__ __launch_bounds__(LMI_FORM_W) void k_lmi_form(const double* __restric
                                                          const double* __restrict__ x, double* __restrict__ A,
                                                          long long m, long long n, long long c0, int mode,
                                                          const LmiState* __restrict__ st) {
-    if (st->pos1) return;
+    if (st->skip || st->pos1) return;
     const long long i = c0 + blockIdx.x;
     const long long j = c0 + threadIdx.x;
     if (i >= m || j >= m || j > i) return;
@@ -57,6 +58,7 @@ __global__ __launch_bounds__(LMI_FORM_W) void k_lmi_form(const double* __restric
 
 // storage lower triangle + diagonal = 0.0 (the accumulators s start from 0.0, ldlt_mgr.rs:42)
 __global__ __launch_bounds__(256) void k_ldlt_clear(double* __restrict__ S, long long m, LmiState* __restrict__ st) {
+    if (st->skip) return;
     const long long total = m * m;
     for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
          idx += (long long)gridDim.x * blockDim.x) {
@@ -74,7 +76,7 @@ __global__ __launch_bounds__(256) void k_ldlt_clear(double* __restrict__ S, long
 //   below it  storage[j][i] = t  (kept for later, :37)  and  storage[i][j] = t / D[j]  (L[i][j], :38-39).
 __global__ __launch_bounds__(64) void k_ldlt_diag(const double* __restrict__ A, double* __restrict__ S, long long m,
                                                   long long k0, LmiState* __restrict__ st) {
-    if (st->pos1) return;
+    if (st->skip || st->pos1) return;
     __shared__ double Ls[LMI_NB][LMI_NB + 1], Ts[LMI_NB][LMI_NB + 1], Dj;
     __shared__ int failed;
     const int r = threadIdx.x;
@@ -116,7 +118,7 @@ __global__ __launch_bounds__(64) void k_ldlt_diag(const double* __restrict__ A, 
 // Rows below the diagonal block (i >= k1), one row per thread, the block's T values and pivots in LDS.
 __global__ __launch_bounds__(128) void k_ldlt_panel(const double* __restrict__ A, double* __restrict__ S, long long m,
                                                     long long k0, const LmiState* __restrict__ st) {
-    if (st->pos1) return;
+    if (st->skip || st->pos1) return;
     __shared__ double Ts[LMI_NB][LMI_NB + 1], D[LMI_NB];
     const long long k1 = k0 + LMI_NB;  // only called when the block is full (k1 <= m)
     for (int idx = threadIdx.x; idx < LMI_NB * LMI_NB; idx += 128) {
@@ -145,7 +147,7 @@ __global__ __launch_bounds__(128) void k_ldlt_panel(const double* __restrict__ A
 // 64 x 64 tiles, 4 x 4 elements per thread, the panel's L rows and T rows staged in LDS.
 __global__ __launch_bounds__(256) void k_ldlt_update(double* __restrict__ S, long long m, long long k0,
                                                      const LmiState* __restrict__ st) {
-    if (st->pos1) return;
+    if (st->skip || st->pos1) return;
     const long long k1 = k0 + LMI_NB;
     const long long ti = blockIdx.y, tj = blockIdx.x;
     if (tj > ti) return;
@@ -196,7 +198,7 @@ constexpr int LMI_WIT_PER = 8;  // columns per thread: m <= 8192
 __global__ __launch_bounds__(1024) void k_lmi_witness(const double* __restrict__ S, long long m,
                                                       double* __restrict__ v, const LmiState* __restrict__ st) {
     const int p = st->pos1;
-    if (!p) return;
+    if (st->skip || !p) return;
     __shared__ double vk;
     const int t = threadIdx.x;
     double s[LMI_WIT_PER];
@@ -234,7 +236,7 @@ __global__ __launch_bounds__(256) void k_lmi_quad(const double* __restrict__ F, 
                                                   const double* __restrict__ v, double* __restrict__ partial,
                                                   const LmiState* __restrict__ st) {
     const int p = st->pos1;
-    if (!p) return;
+    if (st->skip || !p) return;
     __shared__ double red[4];
     const long long k = blockIdx.x;
     const int chunk = blockIdx.y;
@@ -256,7 +258,7 @@ __global__ __launch_bounds__(256) void k_lmi_quad(const double* __restrict__ F, 
 __global__ __launch_bounds__(256) void k_lmi_quad_reduce(long long n, const double* __restrict__ partial,
                                                          double* __restrict__ g, int mode,
                                                          const LmiState* __restrict__ st) {
-    if (!st->pos1) return;
+    if (st->skip || !st->pos1) return;
     const long long k = (long long)blockIdx.x * 256 + threadIdx.x;
     if (k >= n) return;
     double s = 0.0;

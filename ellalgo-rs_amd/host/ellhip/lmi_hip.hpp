@@ -61,6 +61,7 @@ class LmiHandle {
     }
     std::size_t n() const { return n_; }
     std::size_t m() const { return m_; }
+    ellhip_lmi* handle() { return h_; }
 
   private:
     ellhip_lmi* h_ = nullptr;
@@ -110,6 +111,8 @@ class LMIOracleHip {
     }
     void update(double) {}  // OracleFeas::update default (src/cutting_plane.rs:125)
     std::pair<std::size_t, std::size_t> pos() const { return h_.pos(); }
+    std::size_t ndim() const { return h_.n(); }
+    ellhip_lmi* handle() { return h_.handle(); }  // for LmiLoopHip (lmi_loop_hip.hpp)
 
   private:
     detail::LmiHandle h_;
@@ -125,6 +128,8 @@ class LMI0OracleHip {
         if (!h_.assess(&x, g, ep)) return std::nullopt;
         return std::make_pair(std::move(g), ep);
     }
+    std::size_t ndim() const { return h_.n(); }
+    ellhip_lmi* handle() { return h_.handle(); }
 
   private:
     detail::LmiHandle h_;
