@@ -1,7 +1,8 @@
 """Python mirror of the batched device-resident LMI cutting-plane loop (include/ellhip_batch_lmi.h): B independent
 problems `min c'x  s.t.  B_j - sum_k x_k F_jk > 0` (or, without mat_b, `sum_k x_k F_jk > 0`), each with its own
-round-robin oracle (tests/lmi_tests.rs:142-171 generalised to J blocks) and its own ellipsoid of an `EllBatch`, solved by
-one kernel per chunk of iterations.  Bit-identical to the CPU arithmetic."""
+round-robin oracle (tests/lmi_tests.rs:142-171 generalised to J blocks) and its own ellipsoid of an `EllBatch` or an
+`EllStableBatch` (include/ellhip_batch_stable_loops.h), solved by one kernel per chunk of iterations.  Bit-identical to the
+CPU arithmetic."""
 from __future__ import annotations
 
 import ctypes as C
@@ -71,15 +72,16 @@ class BatchLmiProblem:
         return grad, beta, station, gamma
 
     def optim(self, spaces, gamma, max_iters: int, tol: float):
-        """cutting_plane_optim per problem on `spaces` (an EllBatch).  Returns (x_best [B][n] with NaN rows where there
+        """cutting_plane_optim per problem on `spaces` (an EllBatch or an EllStableBatch).  Returns (x_best [B][n] with NaN rows where there
         is none, has_best [B], niter [B], gamma [B], status [B])."""
         gamma = np.array(np.broadcast_to(np.asarray(gamma, dtype=np.float64), (self.B,)))
         x_best = np.full((self.B, self.n), np.nan)
         has = np.empty(self.B, dtype=np.int32)
         niter = np.empty(self.B, dtype=np.int64)
         status = np.empty(self.B, dtype=np.int32)
-        capi.check(self._lib.ellhip_batch_lmi_optim(spaces._h, self._h, _p(gamma), int(max_iters), float(tol), _p(x_best),
-                                                    _p(has), _p(niter), _p(status)), "ellhip_batch_lmi_optim")
+        entry = capi.batch_loop_entry(spaces, "ellhip_batch_lmi_optim")
+        capi.check(getattr(self._lib, entry)(spaces._h, self._h, _p(gamma), int(max_iters), float(tol), _p(x_best), _p(has),
+                                             _p(niter), _p(status)), entry)
         return x_best, has, niter, gamma, status
 
     def feas(self, spaces, max_iters: int, tol: float):
@@ -89,6 +91,7 @@ class BatchLmiProblem:
         ok = np.empty(self.B, dtype=np.int32)
         niter = np.empty(self.B, dtype=np.int64)
         status = np.empty(self.B, dtype=np.int32)
-        capi.check(self._lib.ellhip_batch_lmi_feas(spaces._h, self._h, int(max_iters), float(tol), _p(x), _p(ok), _p(niter),
-                                                   _p(status)), "ellhip_batch_lmi_feas")
+        entry = capi.batch_loop_entry(spaces, "ellhip_batch_lmi_feas")
+        capi.check(getattr(self._lib, entry)(spaces._h, self._h, int(max_iters), float(tol), _p(x), _p(ok), _p(niter),
+                                             _p(status)), entry)
         return x, ok, niter, status

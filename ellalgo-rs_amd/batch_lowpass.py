@@ -1,7 +1,8 @@
 """Python mirror of the batched device-resident low-pass filter design loop (include/ellhip_batch_lowpass.h): B
 independent `LowpassOracle`s (src/oracles/lowpass_oracle.rs) of one filter length n <= 128, each with its own band edges,
-ripple limits and round-robin cursors and its own ellipsoid of an `EllBatch`, over one shared 15n x n table; solved by one
-kernel per chunk of iterations.  Bit-identical to the CPU arithmetic."""
+ripple limits and round-robin cursors and its own ellipsoid of an `EllBatch` or an `EllStableBatch`
+(include/ellhip_batch_stable_loops.h), over one shared 15n x n table; solved by one kernel per chunk of iterations.
+Bit-identical to the CPU arithmetic."""
 from __future__ import annotations
 
 import ctypes as C
@@ -88,16 +89,16 @@ class BatchLowpassProblem:
         return grad, beta0, has1, beta1, shrunk, gamma, rc
 
     def optim(self, batch, gamma, max_iters: int, tol: float):
-        """cutting_plane_optim per problem on `batch` (an EllBatch).  Returns (x_best [B][n] with NaN rows where there is
-        none, has_best [B], niter [B], gamma [B], status [B])."""
+        """cutting_plane_optim per problem on `batch` (an EllBatch or an EllStableBatch).  Returns (x_best [B][n] with NaN
+        rows where there is none, has_best [B], niter [B], gamma [B], status [B])."""
         gamma = np.array(np.broadcast_to(np.asarray(gamma, dtype=np.float64), (self.B,)))
         x_best = np.full((self.B, self.n), np.nan)
         has = np.empty(self.B, dtype=np.int32)
         niter = np.empty(self.B, dtype=np.int64)
         status = np.empty(self.B, dtype=np.int32)
-        capi.check(self._lib.ellhip_batch_lowpass_optim(batch._h, self._h, _p(gamma), int(max_iters), float(tol),
-                                                        _p(x_best), _p(has), _p(niter), _p(status)),
-                   "ellhip_batch_lowpass_optim")
+        entry = capi.batch_loop_entry(batch, "ellhip_batch_lowpass_optim")
+        capi.check(getattr(self._lib, entry)(batch._h, self._h, _p(gamma), int(max_iters), float(tol), _p(x_best), _p(has),
+                                             _p(niter), _p(status)), entry)
         return x_best, has, niter, gamma, status
 
     def feas(self, batch, max_iters: int, tol: float):
@@ -107,6 +108,7 @@ class BatchLowpassProblem:
         ok = np.empty(self.B, dtype=np.int32)
         niter = np.empty(self.B, dtype=np.int64)
         status = np.empty(self.B, dtype=np.int32)
-        capi.check(self._lib.ellhip_batch_lowpass_feas(batch._h, self._h, int(max_iters), float(tol), _p(x), _p(ok),
-                                                       _p(niter), _p(status)), "ellhip_batch_lowpass_feas")
+        entry = capi.batch_loop_entry(batch, "ellhip_batch_lowpass_feas")
+        capi.check(getattr(self._lib, entry)(batch._h, self._h, int(max_iters), float(tol), _p(x), _p(ok), _p(niter),
+                                             _p(status)), entry)
         return x, ok, niter, status

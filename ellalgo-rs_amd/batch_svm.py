@@ -67,13 +67,14 @@ class BatchSvmProblem:
         return idx, val
 
     def optim(self, batch, gamma, max_iters: int, tol: float):
-        """cutting_plane_optim per problem on `batch` (an EllBatch of dimension nfeat + 1).  Returns (x_best [B][n] with
-        NaN rows where there is none, has_best [B], niter [B], gamma [B], status [B])."""
+        """cutting_plane_optim per problem on `batch` (an EllBatch or an EllStableBatch of dimension nfeat + 1).  Returns
+        (x_best [B][n] with NaN rows where there is none, has_best [B], niter [B], gamma [B], status [B])."""
         gamma = np.array(np.broadcast_to(np.asarray(gamma, dtype=np.float64), (self.B,)))
         x_best = np.full((self.B, self.n), np.nan)
         has = np.empty(self.B, dtype=np.int32)
         niter = np.empty(self.B, dtype=np.int64)
         status = np.empty(self.B, dtype=np.int32)
-        capi.check(self._lib.ellhip_batch_svm_optim(batch._h, self._h, _p(gamma), int(max_iters), float(tol), _p(x_best),
-                                                    _p(has), _p(niter), _p(status)), "ellhip_batch_svm_optim")
+        entry = capi.batch_loop_entry(batch, "ellhip_batch_svm_optim")
+        capi.check(getattr(self._lib, entry)(batch._h, self._h, _p(gamma), int(max_iters), float(tol), _p(x_best), _p(has),
+                                             _p(niter), _p(status)), entry)
         return x_best, has, niter, gamma, status

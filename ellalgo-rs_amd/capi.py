@@ -89,6 +89,13 @@ BATCH_SVM_EXPORTS = [
     "ellhip_batch_svm_last", "ellhip_batch_svm_optim", "ellhip_batch_svm_set_chunk",
 ]
 
+# every symbol include/ellhip_batch_stable_loops.h declares (kept apart from EXPORTS, like SVM_EXPORTS): the batched loops
+# of the three headers above on EllStable batch handles
+BATCH_STABLE_LOOP_EXPORTS = [
+    "ellhip_batch_lmi_optim_stable", "ellhip_batch_lmi_feas_stable", "ellhip_batch_lowpass_optim_stable",
+    "ellhip_batch_lowpass_feas_stable", "ellhip_batch_svm_optim_stable",
+]
+
 
 class EllHipError(RuntimeError):
     pass
@@ -326,12 +333,25 @@ def load():
         "ellhip_lmi_loop_assess_feas": (i32, [vp, vp, vp, C.POINTER(dbl), C.POINTER(i32)]),
         "ellhip_lmi_loop_optim": (i32, [vp, vp, C.POINTER(dbl), i64, dbl, vp, C.POINTER(i32), C.POINTER(i64)]),
         "ellhip_lmi_loop_feas": (i32, [vp, vp, i64, dbl, vp, C.POINTER(i32), C.POINTER(i64)]),
+        # include/ellhip_batch_stable_loops.h (each as its Ell counterpart)
+        "ellhip_batch_lmi_optim_stable": (i32, [vp, vp, vp, i64, dbl, vp, vp, vp, vp]),
+        "ellhip_batch_lmi_feas_stable": (i32, [vp, vp, i64, dbl, vp, vp, vp, vp]),
+        "ellhip_batch_lowpass_optim_stable": (i32, [vp, vp, vp, i64, dbl, vp, vp, vp, vp]),
+        "ellhip_batch_lowpass_feas_stable": (i32, [vp, vp, i64, dbl, vp, vp, vp, vp]),
+        "ellhip_batch_svm_optim_stable": (i32, [vp, vp, vp, i64, dbl, vp, vp, vp, vp]),
     }
-    for name in EXPORTS + SVM_EXPORTS + BATCH_LMI_EXPORTS + BATCH_LOWPASS_EXPORTS + BATCH_SVM_EXPORTS + LMI_LOOP_EXPORTS:
+    for name in (EXPORTS + SVM_EXPORTS + BATCH_LMI_EXPORTS + BATCH_LOWPASS_EXPORTS + BATCH_SVM_EXPORTS + LMI_LOOP_EXPORTS +
+                 BATCH_STABLE_LOOP_EXPORTS):
         fn = getattr(L, name)  # AttributeError if the library does not export it
         fn.restype, fn.argtypes = sig[name]
     _lib = L
     return L
+
+
+def batch_loop_entry(batch, name: str) -> str:
+    """The entry point that runs loop `name` on `batch`: the Ell one, or its `_stable` sibling
+    (include/ellhip_batch_stable_loops.h) for an EllStable batch handle."""
+    return name + "_stable" if batch.variant == SPACE_ELL_STABLE else name
 
 
 def check(rc: int, what: str = "") -> int:

@@ -37,7 +37,7 @@ constexpr size_t BATCH_LMI_LDS_MAX = 159 * 1024;
 template <class K>
 int batch_lmi_allow_lds(K kernel, int device, int slot, size_t bytes) {
     constexpr int MAXDEV = 64;
-    static std::atomic<int> granted[MAXDEV][3];
+    static std::atomic<int> granted[MAXDEV][6];  // T = 64, 128, 256 on Ell, then on EllStable
     const bool known = device >= 0 && device < MAXDEV;
     if (known && (int)bytes <= granted[device][slot].load()) return 0;
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
@@ -48,19 +48,65 @@ int batch_lmi_allow_lds(K kernel, int device, int slot, size_t bytes) {
     return 0;
 }
 
+// How a loop kernel is launched on a batch handle.  An Ell handle is launched as the batch engine shaped it.  An EllStable
+// handle is shaped for k_batch_update_stable's one lane per ellipsoid (one wave, up to 64 ellipsoids); the loop kernels
+// give an instance n threads, so they take the Ell rule for T and epw with batch_stable_apply_lds_doubles in it.  slot:
+// the entry of batch_lmi_allow_lds's table (the Ell and EllStable instantiations of a kernel have the same type).
+struct BatchLoopShape {
+    int T = 64, epw = 1, slot = 0;
+    size_t space_doubles = 0;  // LDS doubles of one instance's space
+};
+
+BatchLoopShape batch_loop_shape(const ellhip_batch* s, bool stable) {
+    BatchLoopShape sh;
+    if (!stable) {
+        sh.T = s->T;
+        sh.epw = s->epw;
+        sh.space_doubles = batch_lds_doubles(s->n);
+    } else {
+        sh.T = s->n <= 64 ? 256 : 128;
+        sh.epw = std::min(64, sh.T / s->n);
+        sh.space_doubles = batch_stable_apply_lds_doubles(s->n);
+        while (sh.epw > 1 && (size_t)sh.epw * sh.space_doubles * sizeof(double) > 64 * 1024) sh.epw -= 1;
+    }
+    sh.slot = (sh.T == 64 ? 0 : (sh.T == 128 ? 1 : 2)) + (stable ? 3 : 0);
+    return sh;
+}
+
+// the handle's variant against the entry point's: the plain entry points take Ell handles, the _stable ones EllStable
+int batch_loop_check(const ellhip_batch* s, bool stable, const char* what) {
+    const int want = stable ? ELLHIP_SPACE_ELL_STABLE : ELLHIP_SPACE_ELL;
+    if (s->variant == want) return 0;
+    const std::string msg = std::string(what) + (stable ? ": the _stable entry points take EllStable batch handles only"
+                                                        : ": EllStable batch handles are not supported");
+    return fail(ELLHIP_E_INVALID, msg.c_str());
+}
+
+BatchParams batch_loop_params(const ellhip_batch* s, const BatchLoopShape& sh) {
+    BatchParams P;
+    P.B = s->B;
+    P.n = s->n;
+    P.pitch = batch_pitch(s->n);
+    P.epw = sh.epw;
+    P.K = 0;
+    P.no_defer_trick = s->no_defer_trick;
+    return P;
+}
+
+// stable: the spaces are EllStable (include/ellhip_batch_stable_loops.h)
 int batch_lmi_run(ellhip_batch* s, ellhip_batch_lmi* o, int feas, double* gamma_inout, int64_t max_iters, double tol,
-                  double* x_out, int32_t* has_out, int64_t* niter_out, int32_t* status_out) {
+                  double* x_out, int32_t* has_out, int64_t* niter_out, int32_t* status_out, bool stable = false) {
     if (!s || !o || !has_out || !niter_out || !status_out || (!feas && !gamma_inout))
         return fail(ELLHIP_E_INVALID, "NULL argument");
-    if (s->variant != ELLHIP_SPACE_ELL)
-        return fail(ELLHIP_E_INVALID, "batched LMI loop: EllStable batch handles are not supported");
+    if (const int rc = batch_loop_check(s, stable, "batched LMI loop")) return rc;
     if (s->B != o->B || s->n != o->n) return fail(ELLHIP_E_INVALID, "batched LMI loop: spaces and oracle differ in B or n");
     if (s->device != o->device) return fail(ELLHIP_E_INVALID, "batched LMI loop: spaces and oracle live on different devices");
     if (!feas && !o->L.has_c) return fail(ELLHIP_E_INVALID, "batched LMI loop: optim needs a handle made with c");
     if (feas && o->L.has_c) return fail(ELLHIP_E_INVALID, "batched LMI loop: feas needs a handle made without c");
     if (max_iters < 0) return fail(ELLHIP_E_INVALID, "max_iters must be >= 0");
     const size_t B = (size_t)o->B, n = (size_t)o->n;
-    const size_t lds = (size_t)s->epw * (batch_lds_doubles(s->n) + batch_lmi_lds_doubles(s->n, o->L.mmax)) * sizeof(double);
+    const BatchLoopShape sh = batch_loop_shape(s, stable);
+    const size_t lds = (size_t)sh.epw * (sh.space_doubles + batch_lmi_lds_doubles(s->n, o->L.mmax)) * sizeof(double);
     if (lds > BATCH_LMI_LDS_MAX) return fail(ELLHIP_E_INVALID, "batched LMI loop: this (n, m) needs more LDS than a workgroup has");
     DeviceGuard guard(s->device);
     int* d_has = o->d_ints;
@@ -71,14 +117,8 @@ int batch_lmi_run(ellhip_batch* s, ellhip_batch_lmi* o, int feas, double* gamma_
     HIPCHK(fill_now(o->d_ints, 0, (3 * B + 1) * sizeof(int), s->stream));
     HIPCHK(fill_now(o->d_niter, 0, B * sizeof(long long), s->stream));
     if (!feas) HIPCHK(hipMemcpy(o->d_gamma, gamma_inout, B * sizeof(double), hipMemcpyHostToDevice));
-    BatchParams P;
-    P.B = s->B;
-    P.n = s->n;
-    P.pitch = batch_pitch(s->n);
-    P.epw = s->epw;
-    P.K = 0;
-    P.no_defer_trick = s->no_defer_trick;
-    const unsigned grid = (unsigned)((s->B + s->epw - 1) / s->epw);
+    const BatchParams P = batch_loop_params(s, sh);
+    const unsigned grid = (unsigned)((s->B + sh.epw - 1) / sh.epw);
     const EllCalcDev calc = EllCalcDev::make(s->n, s->use_parallel_cut);
     BatchLmiLoop R;
     R.feas = feas;
@@ -86,18 +126,21 @@ int batch_lmi_run(ellhip_batch* s, ellhip_batch_lmi* o, int feas, double* gamma_
     R.tol = tol;
     for (long long done = 0; done < max_iters; done += o->chunk) {
         R.iters = (int)std::min<long long>(o->chunk, max_iters - done);
-#define BATCH_LMI_GO(TT, SLOT)                                                                                          \
+#define BATCH_LMI_GO(TT, ST)                                                                                           \
     do {                                                                                                                \
-        const int rc_ = batch_lmi_allow_lds(&k_batch_lmi_loop<TT>, s->device, SLOT, lds);                                   \
+        const int rc_ = batch_lmi_allow_lds(&k_batch_lmi_loop<TT, ST>, s->device, sh.slot, lds);                        \
         if (rc_) return rc_;                                                                                            \
-        hipLaunchKernelGGL(k_batch_lmi_loop<TT>, dim3(grid), dim3(TT), lds, s->stream, P, o->L, R, s->d_Q, s->d_xc,     \
-                           s->d_kappa, s->d_tsq, (const double*)o->d_pencil, (const double*)o->d_matb,                  \
+        hipLaunchKernelGGL((k_batch_lmi_loop<TT, ST>), dim3(grid), dim3(TT), lds, s->stream, P, o->L, R, s->d_Q,        \
+                           s->d_xc, s->d_kappa, s->d_tsq, (const double*)o->d_pencil, (const double*)o->d_matb,         \
                            (const double*)o->d_c, o->d_idx, o->d_gamma, o->d_xbest, d_has, o->d_niter, d_stopped,       \
                            d_status, d_nstopped, calc);                                                                 \
     } while (0)
-        if (s->T == 64) BATCH_LMI_GO(64, 0);
-        else if (s->T == 128) BATCH_LMI_GO(128, 1);
-        else BATCH_LMI_GO(256, 2);
+        if (stable) {
+            if (sh.T == 128) BATCH_LMI_GO(128, true);
+            else BATCH_LMI_GO(256, true);
+        } else if (sh.T == 64) BATCH_LMI_GO(64, false);
+        else if (sh.T == 128) BATCH_LMI_GO(128, false);
+        else BATCH_LMI_GO(256, false);
 #undef BATCH_LMI_GO
         HIPCHK(hipGetLastError());
         int nstopped = 0;

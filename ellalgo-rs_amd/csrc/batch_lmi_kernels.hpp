@@ -25,7 +25,7 @@
 // J + 1, M and n; no thread waits on another workgroup.
 #pragma once
 
-#include "batch_kernels.hpp"
+#include "batch_stable_apply.hpp"
 
 namespace ellhip {
 
@@ -203,7 +203,8 @@ struct BatchLmiLoop {
 
 // cutting_plane_optim (src/cutting_plane.rs:286-313) / cutting_plane_feas (:205-227) for every instance of the workgroup.
 // Loop state per instance lives in HBM between launches: idx, gamma, x_best, has_best, niter, stopped, status.
-template <int T>
+// STABLE: the spaces are EllStable buffers and a cut is batch_stable_cut_apply (batch_stable_apply.hpp).
+template <int T, bool STABLE = false>
 __global__ __launch_bounds__(T) void k_batch_lmi_loop(BatchParams P, BatchLmiParams L, BatchLmiLoop R,
                                                       double* __restrict__ Q, double* __restrict__ xc,
                                                       double* __restrict__ kappa, double* __restrict__ tsq,
@@ -221,13 +222,12 @@ __global__ __launch_bounds__(T) void k_batch_lmi_loop(BatchParams P, BatchLmiPar
     const bool active = e < P.epw && b < P.B;
     if (!__syncthreads_or(active && stopped_io[b] == 0)) return;  // all of this workgroup's instances have stopped
 
-    const size_t per = batch_lds_doubles(n);
+    const size_t per = batch_space_lds_doubles<STABLE>(n);
     const size_t lper = batch_lmi_lds_doubles(n, L.mmax);
     const int el = e < P.epw ? e : 0;
     double* q = sm + (size_t)el * per;
     double* g = q + (size_t)n * pitch;
-    double* gt = g + n;
-    double* sc = gt + n;  // as in k_batch_update
+    double* sc = q + batch_space_scalars_at<STABLE>(n);  // as in k_batch_update
     double* lx = sm + (size_t)P.epw * per + (size_t)el * lper;
     double* cl = lx + n;
     double* fa = cl + n;
@@ -259,9 +259,7 @@ __global__ __launch_bounds__(T) void k_batch_lmi_loop(BatchParams P, BatchLmiPar
 
     const bool lane_ok = tid < P.epw && b_first + tid < P.B;
     const int es = tid < P.epw ? tid : 0;
-    const double* g_s = sm + (size_t)es * per + (size_t)n * pitch;
-    const double* gt_s = g_s + n;
-    double* sc_s = const_cast<double*>(gt_s) + n;
+    double* q_s = sm + (size_t)es * per;
     const double* osc_s = sm + (size_t)P.epw * per + (size_t)es * lper + 2 * (size_t)n + (size_t)L.mmax * L.pm + L.mmax;
     const double* F = pencil + (active ? b : 0) * (long long)L.fstride;
     const double* Bm = matb ? matb + (active ? b : 0) * (long long)L.bstride : nullptr;
@@ -280,7 +278,7 @@ __global__ __launch_bounds__(T) void k_batch_lmi_loop(BatchParams P, BatchLmiPar
         const bool lane = lane_ok && osc_s[LO_STOPPED] == 0.0 && !(R.feas && osc_s[LO_STATION] == shrunk_station);
         const int kind = (lane && osc_s[LO_STATION] == shrunk_station) ? CUT_CENTRAL : CUT_BIAS;  // :301-307
         const double beta = lane ? osc_s[LO_BETA] : 0.0;
-        batch_cut_apply(P, calc, upd, i, q, g, gt, sc, xci, lane, g_s, gt_s, sc_s, kind, beta, 0, 0.0, [](int, double) {});
+        batch_space_cut_apply<STABLE>(P, calc, upd, i, q, xci, lane, q_s, kind, beta, 0, 0.0, [](int, double) {});
         if (live && i == 0) {
             if (all_pass) osc[LO_HASBEST] = 1.0;
             bool stop;

@@ -74,19 +74,21 @@ int batch_lowpass_fresh(ellhip_batch_lowpass* o) {
     return 0;
 }
 
+// stable: the spaces are EllStable (include/ellhip_batch_stable_loops.h)
 int batch_lowpass_run(ellhip_batch* s, ellhip_batch_lowpass* o, int feas, double* gamma_inout, int64_t max_iters,
-                      double tol, double* x_out, int32_t* has_out, int64_t* niter_out, int32_t* status_out) {
+                      double tol, double* x_out, int32_t* has_out, int64_t* niter_out, int32_t* status_out,
+                      bool stable = false) {
     if (!s || !o || !has_out || !niter_out || !status_out || (!feas && !gamma_inout))
         return fail(ELLHIP_E_INVALID, "NULL argument");
-    if (s->variant != ELLHIP_SPACE_ELL)
-        return fail(ELLHIP_E_INVALID, "batched lowpass loop: EllStable batch handles are not supported");
+    if (const int rc = batch_loop_check(s, stable, "batched lowpass loop")) return rc;
     if (s->B != o->B || s->n != o->n)
         return fail(ELLHIP_E_INVALID, "batched lowpass loop: spaces and oracle differ in B or n");
     if (s->device != o->device)
         return fail(ELLHIP_E_INVALID, "batched lowpass loop: spaces and oracle live on different devices");
     if (max_iters < 0) return fail(ELLHIP_E_INVALID, "max_iters must be >= 0");
     const size_t B = (size_t)o->B, n = (size_t)o->n;
-    const size_t lds = (size_t)s->epw * (batch_lds_doubles(s->n) + batch_lowpass_lds_doubles(s->n)) * sizeof(double);
+    const BatchLoopShape sh = batch_loop_shape(s, stable);
+    const size_t lds = (size_t)sh.epw * (sh.space_doubles + batch_lowpass_lds_doubles(s->n)) * sizeof(double);
     if (lds > BATCH_LMI_LDS_MAX) return fail(ELLHIP_E_INVALID, "batched lowpass loop: this n needs more LDS than a workgroup has");
     DeviceGuard guard(s->device);
     BatchLpArrays A = batch_lowpass_arrays(o);
@@ -95,14 +97,8 @@ int batch_lowpass_run(ellhip_batch* s, ellhip_batch_lowpass* o, int feas, double
     HIPCHK(fill_now(o->d_ints, 0, (3 * B + 1) * sizeof(int), s->stream));
     HIPCHK(fill_now(o->d_niter, 0, B * sizeof(long long), s->stream));
     if (!feas) HIPCHK(hipMemcpy(o->d_gamma, gamma_inout, B * sizeof(double), hipMemcpyHostToDevice));
-    BatchParams P;
-    P.B = s->B;
-    P.n = s->n;
-    P.pitch = batch_pitch(s->n);
-    P.epw = s->epw;
-    P.K = 0;
-    P.no_defer_trick = s->no_defer_trick;
-    const unsigned grid = (unsigned)((s->B + s->epw - 1) / s->epw);
+    const BatchParams P = batch_loop_params(s, sh);
+    const unsigned grid = (unsigned)((s->B + sh.epw - 1) / sh.epw);
     const EllCalcDev calc = EllCalcDev::make(s->n, s->use_parallel_cut);
     BatchLpLoop R;
     R.feas = feas;
@@ -111,16 +107,19 @@ int batch_lowpass_run(ellhip_batch* s, ellhip_batch_lowpass* o, int feas, double
     R.tol = tol;
     for (long long done = 0; done < max_iters; done += o->chunk) {
         R.iters = (int)std::min<long long>(o->chunk, max_iters - done);
-#define BATCH_LP_GO(TT, SLOT)                                                                                         \
+#define BATCH_LP_GO(TT, ST)                                                                                           \
     do {                                                                                                              \
-        const int rc_ = batch_lmi_allow_lds(&k_batch_lowpass_loop<TT>, s->device, SLOT, lds);                         \
+        const int rc_ = batch_lmi_allow_lds(&k_batch_lowpass_loop<TT, ST>, s->device, sh.slot, lds);                  \
         if (rc_) return rc_;                                                                                          \
-        hipLaunchKernelGGL(k_batch_lowpass_loop<TT>, dim3(grid), dim3(TT), lds, s->stream, P, R, s->d_Q, s->d_xc,     \
-                           s->d_kappa, s->d_tsq, A, calc);                                                            \
+        hipLaunchKernelGGL((k_batch_lowpass_loop<TT, ST>), dim3(grid), dim3(TT), lds, s->stream, P, R, s->d_Q,        \
+                           s->d_xc, s->d_kappa, s->d_tsq, A, calc);                                                   \
     } while (0)
-        if (s->T == 64) BATCH_LP_GO(64, 0);
-        else if (s->T == 128) BATCH_LP_GO(128, 1);
-        else BATCH_LP_GO(256, 2);
+        if (stable) {
+            if (sh.T == 128) BATCH_LP_GO(128, true);
+            else BATCH_LP_GO(256, true);
+        } else if (sh.T == 64) BATCH_LP_GO(64, false);
+        else if (sh.T == 128) BATCH_LP_GO(128, false);
+        else BATCH_LP_GO(256, false);
 #undef BATCH_LP_GO
         HIPCHK(hipGetLastError());
         int nstopped = 0;

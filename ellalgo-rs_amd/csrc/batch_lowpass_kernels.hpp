@@ -29,7 +29,7 @@
 
 #include <climits>
 
-#include "batch_kernels.hpp"
+#include "batch_stable_apply.hpp"
 
 namespace ellhip {
 
@@ -287,7 +287,8 @@ struct BatchLpLoop {
 
 // cutting_plane_optim (src/cutting_plane.rs:286-313) / cutting_plane_feas (:205-227) for every instance of the workgroup.
 // Loop state per instance lives in HBM between launches (BatchLpArrays).
-template <int T>
+// STABLE: the spaces are EllStable buffers and a cut is batch_stable_cut_apply (batch_stable_apply.hpp).
+template <int T, bool STABLE = false>
 __global__ __launch_bounds__(T) void k_batch_lowpass_loop(BatchParams P, BatchLpLoop R, double* __restrict__ Q,
                                                           double* __restrict__ xc, double* __restrict__ kappa,
                                                           double* __restrict__ tsq, BatchLpArrays A, EllCalcDev calc) {
@@ -299,13 +300,12 @@ __global__ __launch_bounds__(T) void k_batch_lowpass_loop(BatchParams P, BatchLp
     const bool active = e < P.epw && b < P.B;
     if (!__syncthreads_or(active && A.stopped[b] == 0)) return;  // all of this workgroup's instances have stopped
 
-    const size_t per = batch_lds_doubles(n);
+    const size_t per = batch_space_lds_doubles<STABLE>(n);
     const size_t lper = batch_lowpass_lds_doubles(n);
     const int el = e < P.epw ? e : 0;
     double* q = sm + (size_t)el * per;
     double* g = q + (size_t)n * pitch;
-    double* gt = g + n;
-    double* sc = gt + n;  // as in k_batch_update
+    double* sc = q + batch_space_scalars_at<STABLE>(n);  // as in k_batch_update
     double* lx = sm + (size_t)P.epw * per + (size_t)el * lper;
     double* osc = lx + n;
 
@@ -345,9 +345,7 @@ __global__ __launch_bounds__(T) void k_batch_lowpass_loop(BatchParams P, BatchLp
 
     const bool lane_ok = tid < P.epw && b_first + tid < P.B;
     const int es = tid < P.epw ? tid : 0;
-    const double* g_s = sm + (size_t)es * per + (size_t)n * pitch;
-    const double* gt_s = g_s + n;
-    double* sc_s = const_cast<double*>(gt_s) + n;
+    double* q_s = sm + (size_t)es * per;
     const double* osc_s = sm + (size_t)P.epw * per + (size_t)es * lper + n;
     const bool optim = R.feas == 0;
 
@@ -371,7 +369,7 @@ __global__ __launch_bounds__(T) void k_batch_lowpass_loop(BatchParams P, BatchLp
         const double b0 = lane ? osc_s[BO_B0] : 0.0;
         const double b1 = lane ? osc_s[BO_B1] : 0.0;
         const int hb1 = lane ? (int)osc_s[BO_HB1] : 0;
-        batch_cut_apply(P, calc, upd, i, q, g, gt, sc, xci, lane, g_s, gt_s, sc_s, kind, b0, hb1, b1, [](int, double) {});
+        batch_space_cut_apply<STABLE>(P, calc, upd, i, q, xci, lane, q_s, kind, b0, hb1, b1, [](int, double) {});
         if (live && i == 0) {
             if (shrunk || found) osc[BO_HASBEST] = 1.0;
             bool stop;

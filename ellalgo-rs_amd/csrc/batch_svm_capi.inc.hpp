@@ -208,19 +208,20 @@ int ellhip_batch_svm_last(ellhip_batch_svm* o, int64_t* min_idx, double* min_val
     return 0;
 }
 
-int ellhip_batch_svm_optim(ellhip_batch* s, ellhip_batch_svm* o, double* gamma_inout, int64_t max_iters, double tol,
-                           double* x_best_out, int32_t* has_best_out, int64_t* niter_out, int32_t* status_out) {
+// stable: the spaces are EllStable (include/ellhip_batch_stable_loops.h)
+static int batch_svm_run(ellhip_batch* s, ellhip_batch_svm* o, double* gamma_inout, int64_t max_iters, double tol,
+                         double* x_best_out, int32_t* has_best_out, int64_t* niter_out, int32_t* status_out, bool stable) {
     if (!s || !o || !gamma_inout || !has_best_out || !niter_out || !status_out)
         return fail(ELLHIP_E_INVALID, "NULL argument");
-    if (s->variant != ELLHIP_SPACE_ELL)
-        return fail(ELLHIP_E_INVALID, "batched svm loop: EllStable batch handles are not supported");
+    if (const int rc = batch_loop_check(s, stable, "batched svm loop")) return rc;
     if (s->B != o->B || s->n != o->n)
         return fail(ELLHIP_E_INVALID, "batched svm loop: spaces and oracle differ in B or n (n = nfeat + 1)");
     if (s->device != o->device)
         return fail(ELLHIP_E_INVALID, "batched svm loop: spaces and oracle live on different devices");
     if (max_iters < 0) return fail(ELLHIP_E_INVALID, "max_iters must be >= 0");
     const size_t B = (size_t)o->B, n = (size_t)o->n;
-    const size_t lds = (size_t)s->epw * (batch_lds_doubles(s->n) + batch_svm_lds_doubles(s->n)) * sizeof(double);
+    const BatchLoopShape sh = batch_loop_shape(s, stable);
+    const size_t lds = (size_t)sh.epw * (sh.space_doubles + batch_svm_lds_doubles(s->n)) * sizeof(double);
     if (lds > BATCH_LMI_LDS_MAX) return fail(ELLHIP_E_INVALID, "batched svm loop: this n needs more LDS than a workgroup has");
     DeviceGuard guard(s->device);
     BatchSvmArrays A = batch_svm_arrays(o);
@@ -229,14 +230,8 @@ int ellhip_batch_svm_optim(ellhip_batch* s, ellhip_batch_svm* o, double* gamma_i
     HIPCHK(fill_now(o->d_ints, 0, (3 * B + 1) * sizeof(int), s->stream));
     HIPCHK(fill_now(o->d_niter, 0, B * sizeof(long long), s->stream));
     HIPCHK(hipMemcpy(o->d_gamma, gamma_inout, B * sizeof(double), hipMemcpyHostToDevice));
-    BatchParams P;
-    P.B = s->B;
-    P.n = s->n;
-    P.pitch = batch_pitch(s->n);
-    P.epw = s->epw;
-    P.K = 0;
-    P.no_defer_trick = s->no_defer_trick;
-    const unsigned grid = (unsigned)((s->B + s->epw - 1) / s->epw);
+    const BatchParams P = batch_loop_params(s, sh);
+    const unsigned grid = (unsigned)((s->B + sh.epw - 1) / sh.epw);
     const EllCalcDev calc = EllCalcDev::make(s->n, s->use_parallel_cut);
     BatchSvmLoop R;
     R.m = o->m;
@@ -245,16 +240,19 @@ int ellhip_batch_svm_optim(ellhip_batch* s, ellhip_batch_svm* o, double* gamma_i
     R.tol = tol;
     for (long long done = 0; done < max_iters; done += o->chunk) {
         R.iters = (int)std::min<long long>(o->chunk, max_iters - done);
-#define BATCH_SVM_GO(TT, SLOT)                                                                                        \
+#define BATCH_SVM_GO(TT, ST)                                                                                          \
     do {                                                                                                              \
-        const int rc_ = batch_lmi_allow_lds(&k_batch_svm_loop<TT>, s->device, SLOT, lds);                             \
+        const int rc_ = batch_lmi_allow_lds(&k_batch_svm_loop<TT, ST>, s->device, sh.slot, lds);                      \
         if (rc_) return rc_;                                                                                          \
-        hipLaunchKernelGGL(k_batch_svm_loop<TT>, dim3(grid), dim3(TT), lds, s->stream, P, R, s->d_Q, s->d_xc,         \
+        hipLaunchKernelGGL((k_batch_svm_loop<TT, ST>), dim3(grid), dim3(TT), lds, s->stream, P, R, s->d_Q, s->d_xc,   \
                            s->d_kappa, s->d_tsq, A, calc);                                                            \
     } while (0)
-        if (s->T == 64) BATCH_SVM_GO(64, 0);
-        else if (s->T == 128) BATCH_SVM_GO(128, 1);
-        else BATCH_SVM_GO(256, 2);
+        if (stable) {
+            if (sh.T == 128) BATCH_SVM_GO(128, true);
+            else BATCH_SVM_GO(256, true);
+        } else if (sh.T == 64) BATCH_SVM_GO(64, false);
+        else if (sh.T == 128) BATCH_SVM_GO(128, false);
+        else BATCH_SVM_GO(256, false);
 #undef BATCH_SVM_GO
         HIPCHK(hipGetLastError());
         int nstopped = 0;
@@ -279,6 +277,11 @@ int ellhip_batch_svm_optim(ellhip_batch* s, ellhip_batch_svm* o, double* gamma_i
             if (has[b]) memcpy(x_best_out + b * n, xb.data() + b * n, n * sizeof(double));
     }
     return 0;
+}
+
+int ellhip_batch_svm_optim(ellhip_batch* s, ellhip_batch_svm* o, double* gamma_inout, int64_t max_iters, double tol,
+                           double* x_best_out, int32_t* has_best_out, int64_t* niter_out, int32_t* status_out) {
+    return batch_svm_run(s, o, gamma_inout, max_iters, tol, x_best_out, has_best_out, niter_out, status_out, false);
 }
 
 int ellhip_batch_svm_set_chunk(ellhip_batch_svm* o, int64_t iters) {

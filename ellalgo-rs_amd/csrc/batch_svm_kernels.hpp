@@ -30,7 +30,7 @@
 
 #include <climits>
 
-#include "batch_kernels.hpp"
+#include "batch_stable_apply.hpp"
 
 namespace ellhip {
 
@@ -161,8 +161,9 @@ struct BatchSvmLoop {
 };
 
 // cutting_plane_optim (src/cutting_plane.rs:286-313) for every instance of the workgroup.  Loop state per instance lives in
-// HBM between launches (BatchSvmArrays).
-template <int T>
+// HBM between launches (BatchSvmArrays).  STABLE: the spaces are EllStable buffers and a cut is batch_stable_cut_apply
+// (batch_stable_apply.hpp).
+template <int T, bool STABLE = false>
 __global__ __launch_bounds__(T) void k_batch_svm_loop(BatchParams P, BatchSvmLoop R, double* __restrict__ Q,
                                                       double* __restrict__ xc, double* __restrict__ kappa,
                                                       double* __restrict__ tsq, BatchSvmArrays A, EllCalcDev calc) {
@@ -174,13 +175,12 @@ __global__ __launch_bounds__(T) void k_batch_svm_loop(BatchParams P, BatchSvmLoo
     const bool active = e < P.epw && b < P.B;
     if (!__syncthreads_or(active && A.stopped[b] == 0)) return;  // all of this workgroup's instances have stopped
 
-    const size_t per = batch_lds_doubles(n);
+    const size_t per = batch_space_lds_doubles<STABLE>(n);
     const size_t lper = batch_svm_lds_doubles(n);
     const int el = e < P.epw ? e : 0;
     double* q = sm + (size_t)el * per;
     double* g = q + (size_t)n * pitch;
-    double* gt = g + n;
-    double* sc = gt + n;  // as in k_batch_update
+    double* sc = q + batch_space_scalars_at<STABLE>(n);  // as in k_batch_update
     double* lx = sm + (size_t)P.epw * per + (size_t)el * lper;
     double* osc = lx + n;
 
@@ -214,9 +214,7 @@ __global__ __launch_bounds__(T) void k_batch_svm_loop(BatchParams P, BatchSvmLoo
 
     const bool lane_ok = tid < P.epw && b_first + tid < P.B;
     const int es = tid < P.epw ? tid : 0;
-    const double* g_s = sm + (size_t)es * per + (size_t)n * pitch;
-    const double* gt_s = g_s + n;
-    double* sc_s = const_cast<double*>(gt_s) + n;
+    double* q_s = sm + (size_t)es * per;
     const double* osc_s = sm + (size_t)P.epw * per + (size_t)es * lper + n;
 
     for (int it = 0; it < R.iters; ++it) {
@@ -227,8 +225,8 @@ __global__ __launch_bounds__(T) void k_batch_svm_loop(BatchParams P, BatchSvmLoo
         if (live) xb = xci;  // x_best = Some(space.xc())                    src/cutting_plane.rs:303
         const bool lane = lane_ok && osc_s[SV_STOPPED] == 0.0;
         const double b0 = lane ? osc_s[SV_B0] : 0.0;
-        batch_cut_apply(P, calc, live, i, q, g, gt, sc, xci, lane, g_s, gt_s, sc_s, CUT_CENTRAL, b0, 0, 0.0,
-                        [](int, double) {});  //                              :304
+        batch_space_cut_apply<STABLE>(P, calc, live, i, q, xci, lane, q_s, CUT_CENTRAL, b0, 0, 0.0,
+                                      [](int, double) {});  //                :304
         if (live && i == 0) {
             osc[SV_HASBEST] = 1.0;
             bool stop;

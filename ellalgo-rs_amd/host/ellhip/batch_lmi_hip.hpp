@@ -9,7 +9,7 @@
 #include <optional>
 #include <vector>
 
-#include "../../../include/ellhip_batch_lmi.h"
+#include "../../../include/ellhip_batch_stable_loops.h"
 #include "ell_batch_hip.hpp"
 
 namespace ellhip {
@@ -64,24 +64,31 @@ class BatchLmiHip {
     std::size_t blocks() const { return J_; }
 
     // cutting_plane_optim (src/cutting_plane.rs:286-313) for every problem; gamma has B entries and is updated
-    BatchLmiResult optim(EllBatchHip& spaces, Arr& gamma, const Options& options) {
+    // (spaces: an EllBatchHip, or an EllStableBatchHip through include/ellhip_batch_stable_loops.h)
+    template <int VARIANT>
+    BatchLmiResult optim(BatchHip<VARIANT>& spaces, Arr& gamma, const Options& options) {
+        constexpr bool stable = VARIANT == ELLHIP_SPACE_ELL_STABLE;
         if (gamma.size() != B_) throw Error(ELLHIP_E_INVALID, "gamma must have B entries");
         Arr x(B_ * n_);
         std::vector<int32_t> has(B_), status(B_);
         std::vector<int64_t> niter(B_);
-        check(ellhip_batch_lmi_optim(spaces.handle(), h_, gamma.data(), (int64_t)options.max_iters, options.tolerance,
-                                     x.data(), has.data(), niter.data(), status.data()),
-              "ellhip_batch_lmi_optim");
+        check((stable ? ellhip_batch_lmi_optim_stable : ellhip_batch_lmi_optim)(
+                  spaces.handle(), h_, gamma.data(), (int64_t)options.max_iters, options.tolerance, x.data(), has.data(),
+                  niter.data(), status.data()),
+              stable ? "ellhip_batch_lmi_optim_stable" : "ellhip_batch_lmi_optim");
         return result(x, has, niter, status);
     }
     // cutting_plane_feas (:205-227) for every problem
-    BatchLmiResult feas(EllBatchHip& spaces, const Options& options) {
+    template <int VARIANT>
+    BatchLmiResult feas(BatchHip<VARIANT>& spaces, const Options& options) {
+        constexpr bool stable = VARIANT == ELLHIP_SPACE_ELL_STABLE;
         Arr x(B_ * n_);
         std::vector<int32_t> has(B_), status(B_);
         std::vector<int64_t> niter(B_);
-        check(ellhip_batch_lmi_feas(spaces.handle(), h_, (int64_t)options.max_iters, options.tolerance, x.data(),
-                                    has.data(), niter.data(), status.data()),
-              "ellhip_batch_lmi_feas");
+        check((stable ? ellhip_batch_lmi_feas_stable : ellhip_batch_lmi_feas)(
+                  spaces.handle(), h_, (int64_t)options.max_iters, options.tolerance, x.data(), has.data(), niter.data(),
+                  status.data()),
+              stable ? "ellhip_batch_lmi_feas_stable" : "ellhip_batch_lmi_feas");
         return result(x, has, niter, status);
     }
     std::vector<int32_t> idx() const {

@@ -10,7 +10,7 @@
 #include <utility>
 #include <vector>
 
-#include "../../../include/ellhip_batch_lowpass.h"
+#include "../../../include/ellhip_batch_stable_loops.h"
 #include "ell_batch_hip.hpp"
 
 namespace ellhip {
@@ -92,24 +92,31 @@ class BatchLowpassHip {
         return r;
     }
     // cutting_plane_optim (src/cutting_plane.rs:286-313) for every problem; gamma has B entries and is updated
-    BatchLowpassResult optim(EllBatchHip& spaces, Arr& gamma, const Options& options) {
+    // (spaces: an EllBatchHip, or an EllStableBatchHip through include/ellhip_batch_stable_loops.h)
+    template <int VARIANT>
+    BatchLowpassResult optim(BatchHip<VARIANT>& spaces, Arr& gamma, const Options& options) {
+        constexpr bool stable = VARIANT == ELLHIP_SPACE_ELL_STABLE;
         if (gamma.size() != B_) throw Error(ELLHIP_E_INVALID, "gamma must have B entries");
         Arr x(B_ * n_);
         std::vector<int32_t> has(B_), status(B_);
         std::vector<int64_t> niter(B_);
-        check(ellhip_batch_lowpass_optim(spaces.handle(), h_, gamma.data(), (int64_t)options.max_iters, options.tolerance,
-                                         x.data(), has.data(), niter.data(), status.data()),
-              "ellhip_batch_lowpass_optim");
+        check((stable ? ellhip_batch_lowpass_optim_stable : ellhip_batch_lowpass_optim)(
+                  spaces.handle(), h_, gamma.data(), (int64_t)options.max_iters, options.tolerance, x.data(), has.data(),
+                  niter.data(), status.data()),
+              stable ? "ellhip_batch_lowpass_optim_stable" : "ellhip_batch_lowpass_optim");
         return result(x, has, niter, status);
     }
     // cutting_plane_feas (:205-227) for every problem
-    BatchLowpassResult feas(EllBatchHip& spaces, const Options& options) {
+    template <int VARIANT>
+    BatchLowpassResult feas(BatchHip<VARIANT>& spaces, const Options& options) {
+        constexpr bool stable = VARIANT == ELLHIP_SPACE_ELL_STABLE;
         Arr x(B_ * n_);
         std::vector<int32_t> has(B_), status(B_);
         std::vector<int64_t> niter(B_);
-        check(ellhip_batch_lowpass_feas(spaces.handle(), h_, (int64_t)options.max_iters, options.tolerance, x.data(),
-                                        has.data(), niter.data(), status.data()),
-              "ellhip_batch_lowpass_feas");
+        check((stable ? ellhip_batch_lowpass_feas_stable : ellhip_batch_lowpass_feas)(
+                  spaces.handle(), h_, (int64_t)options.max_iters, options.tolerance, x.data(), has.data(), niter.data(),
+                  status.data()),
+              stable ? "ellhip_batch_lowpass_feas_stable" : "ellhip_batch_lowpass_feas");
         return result(x, has, niter, status);
     }
     std::vector<Fields> fields() const {

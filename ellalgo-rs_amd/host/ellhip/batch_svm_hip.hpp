@@ -10,7 +10,7 @@
 #include <utility>
 #include <vector>
 
-#include "../../../include/ellhip_batch_svm.h"
+#include "../../../include/ellhip_batch_stable_loops.h"
 #include "ell_batch_hip.hpp"
 
 namespace ellhip {
@@ -78,14 +78,18 @@ class BatchSvmHip {
         return r;
     }
     // cutting_plane_optim (src/cutting_plane.rs:286-313) for every problem; gamma has B entries and is updated
-    BatchSvmResult optim(EllBatchHip& spaces, Arr& gamma, const Options& options) {
+    // (spaces: an EllBatchHip, or an EllStableBatchHip through include/ellhip_batch_stable_loops.h)
+    template <int VARIANT>
+    BatchSvmResult optim(BatchHip<VARIANT>& spaces, Arr& gamma, const Options& options) {
+        constexpr bool stable = VARIANT == ELLHIP_SPACE_ELL_STABLE;
         if (gamma.size() != B_) throw Error(ELLHIP_E_INVALID, "gamma must have B entries");
         Arr x(B_ * n_);
         std::vector<int32_t> has(B_), status(B_);
         std::vector<int64_t> niter(B_);
-        check(ellhip_batch_svm_optim(spaces.handle(), h_, gamma.data(), (int64_t)options.max_iters, options.tolerance,
-                                     x.data(), has.data(), niter.data(), status.data()),
-              "ellhip_batch_svm_optim");
+        check((stable ? ellhip_batch_svm_optim_stable : ellhip_batch_svm_optim)(
+                  spaces.handle(), h_, gamma.data(), (int64_t)options.max_iters, options.tolerance, x.data(), has.data(),
+                  niter.data(), status.data()),
+              stable ? "ellhip_batch_svm_optim_stable" : "ellhip_batch_svm_optim");
         BatchSvmResult r;
         for (std::size_t b = 0; b < B_; ++b) {
             if (has[b]) r.x_best.emplace_back(Arr(x.begin() + b * n_, x.begin() + (b + 1) * n_));

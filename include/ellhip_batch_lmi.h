@@ -21,7 +21,8 @@
  * oracle and update in the same kernel, no host in the loop.  All arithmetic is + - * / in the reference's fold order,
  * so iteration counts, x_best, gamma and the spaces afterwards are bit-identical to the CPU arithmetic.
  *
- * `EllStable` batch handles are out of scope: the loop entry points refuse them with ELLHIP_E_INVALID.
+ * `EllStable` batch handles belong to ellhip_batch_stable_loops.h (ellhip_batch_lmi_optim_stable, _feas_stable): the loop
+ * entry points here refuse them with ELLHIP_E_INVALID.
  *
  * LDS: a workgroup holds `epw` problems, epw as the batch engine chooses it for n (ellhip_batch.h).  With
  * p(k) = k | 1 and M = max_j m_j it needs

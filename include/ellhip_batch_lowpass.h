@@ -18,7 +18,7 @@
  * spaces afterwards are bit-identical to the CPU arithmetic.  (The single-problem oracle of ellhip_lowpass.h sums a row
  * in another order and is close to 1e-12 only; it serves n in the thousands, this one sweeps of small problems.)
  *
- * `EllStable` batch handles are out of scope: the loop entry points refuse them with ELLHIP_E_INVALID.
+ * `EllStable` batch handles belong to ellhip_batch_stable_loops.h: the loop entry points refuse them with ELLHIP_E_INVALID.
  *
  * LDS: a workgroup holds `epw` problems, epw as the batch engine chooses it for n (ellhip_batch.h).  With p(k) = k | 1
  * it needs

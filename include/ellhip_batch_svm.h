@@ -18,7 +18,8 @@
  * afterwards are bit-identical to the CPU arithmetic.  (ellhip_svm.h serves one problem with millions of samples; this
  * one sweeps of small problems.)  SvmOracle implements OracleOptim only, so there is no `_feas` entry point.
  *
- * `EllStable` batch handles are out of scope: ellhip_batch_svm_optim refuses them with ELLHIP_E_INVALID.
+ * `EllStable` batch handles belong to ellhip_batch_stable_loops.h (ellhip_batch_svm_optim_stable): ellhip_batch_svm_optim
+ * refuses them with ELLHIP_E_INVALID.
  *
  * Memory: the table is kept feature-major on the device, nfeat x ld doubles per table with ld = m rounded up to 8; it is
  * transposed on the device at create from bounded slabs of the caller's rows.

@@ -1,7 +1,7 @@
 """The batched device-resident low-pass design loop against the two other ways to solve the same instances: one JSON line.
 
   python tools/batch_lowpass_bench.py [--shapes 16:16384,32:4096,32:65536,64:1024] [--reps 3] [--warmup 1]
-                                      [--host-b 64] [--skip-host]
+                                      [--host-b 64] [--skip-host] [--space ell|stable]
 
 Workload (tests/batch_lowpass_reference.py: family): B specifications of one filter length n, wp = 0.08 + 0.01 (s % 6),
 ws = wp + 0.08 + 0.01 (s % 3), d = 0.02 + 0.01 (s % 6), limits ((1 - d)^2, (1 + d)^2, 0.1); Ell::new_with_scalar(40, 0),
@@ -21,6 +21,10 @@ Per shape:
            instance that has stopped receives a no-op cut, beta = +inf).  On the first --host-b instances, once.
 Every device result must equal the CPU's bit for bit (niter, gamma, status, x_best), and so must the host-driven form;
 the tool checks it.
+
+--space stable runs the same three forms on EllStable spaces (include/ellhip_batch_stable_loops.h): the device loop on an
+EllStableBatch, the CPU oracle's loop over its EllStable, and the host-driven form over ellhip_batch_update on an
+EllStableBatch (a stopped instance receives a cut that fails, beta = +inf).
 """
 from __future__ import annotations
 
@@ -39,6 +43,18 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 MAX_ITERS, TOL, KAPPA = 50000, 1e-14, 40.0
+STABLE = False  # --space stable
+
+
+def new_batch(pkg, n, B):
+    return (pkg.EllStableBatch if STABLE else pkg.EllBatch).new_with_scalar(np.full(B, KAPPA), np.zeros((B, n)), device=0)
+
+
+def fresh(ref, n, consts):
+    omega, space = ref.fresh(n, consts)
+    if STABLE:
+        space = ref.O.OracleEllStable.new_with_scalar(KAPPA, np.zeros(n))
+    return omega, space
 
 
 def rounds_of(niter):
@@ -48,7 +64,7 @@ def rounds_of(niter):
 def device_run(pkg, ref, n, B):
     consts = [ref.family(s) for s in range(B)]
     prob = pkg.BatchLowpassProblem(n, *ref.columns(consts), device=0)
-    batch = pkg.EllBatch.new_with_scalar(np.full(B, KAPPA), np.zeros((B, n)), device=0)
+    batch = new_batch(pkg, n, B)
     gamma0 = np.array([c[4] for c in consts])
     t0 = time.perf_counter()
     x_best, has, niter, gamma, status = prob.optim(batch, gamma0, MAX_ITERS, TOL)
@@ -60,14 +76,14 @@ def cpu_run(ref, n):
     recs, secs, rounds, rows = [], 0.0, 0, 0
     for s in range(6):
         consts = ref.family(s)
-        omega, space = ref.fresh(n, consts)
+        omega, space = fresh(ref, n, consts)
         t0 = time.perf_counter()
         xb, niter, gamma, status = omega.cutting_plane_optim(space, consts[4], MAX_ITERS, TOL)
         secs += time.perf_counter() - t0
         recs.append(dict(x_best=xb, niter=niter, gamma=gamma, status=status))
         rounds += niter + 1 if niter < MAX_ITERS else niter
         # the rows the walk visits, call by call, on a second oracle (the loop above is the timed one)
-        omega2, space2 = ref.fresh(n, consts)
+        omega2, space2 = fresh(ref, n, consts)
         g2 = consts[4]
         for _ in range(rounds_of(np.array([niter]))):
             x = np.array(space2.xc)
@@ -84,7 +100,7 @@ def host_run(pkg, ref, n, B):
     """the form that needs no device loop: CPU oracle per instance, ellhip_batch_update with K = 1 per iteration"""
     consts = [ref.family(s) for s in range(B)]
     omegas = [ref.O.OracleLowpass(n, *c) for c in consts]
-    batch = pkg.EllBatch.new_with_scalar(np.full(B, KAPPA), np.zeros((B, n)), device=0)
+    batch = new_batch(pkg, n, B)
     gamma = np.array([c[4] for c in consts])
     niter = np.full(B, MAX_ITERS, dtype=np.int64)
     live = np.ones(B, dtype=bool)
@@ -122,11 +138,14 @@ def bench(pkg, ref, n, B, reps, warmup, host_b, skip_host):
     for b in range(B):
         r = recs[b % 6]
         assert niter[b] == r["niter"] and gamma[b] == r["gamma"] and status[b] == r["status"], f"device and CPU disagree at {b}"
-        assert r["x_best"] is not None and np.array_equal(x_best[b], r["x_best"]), f"device and CPU disagree at {b}"
+        if r["x_best"] is None:  # (EllStable: the family's members end NoSoln before a best point)
+            assert STABLE and np.isnan(x_best[b]).all(), f"device and CPU disagree at {b}"
+        else:
+            assert np.array_equal(x_best[b], r["x_best"]), f"device and CPU disagree at {b}"
     rounds = rounds_of(niter)
     med = statistics.median(times)
     cpu_rate = cpu_rounds / cpu_s
-    out = {"n": n, "B": B, "niter_min": int(niter.min()), "niter_max": int(niter.max()), "rounds": rounds,
+    out = {"space": "stable" if STABLE else "ell", "n": n, "B": B, "niter_min": int(niter.min()), "niter_max": int(niter.max()), "rounds": rounds,
            "rows_per_iter": cpu_rows / cpu_rounds,
            "device_s": {"median": med, "min": min(times), "max": max(times), "reps": reps},
            "device_iters_per_s": rounds / med, "device_solves_per_s": B / med,
@@ -148,7 +167,10 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--host-b", type=int, default=64)
     ap.add_argument("--skip-host", action="store_true")
+    ap.add_argument("--space", choices=("ell", "stable"), default="ell")
     args = ap.parse_args()
+    global STABLE
+    STABLE = args.space == "stable"
     import ellalgo_rs_amd as pkg
     import batch_lowpass_reference as ref
     if pkg.capi.load().ellhip_device_count() <= 0:

@@ -2,6 +2,7 @@
 
   python tools/batch_svm_bench.py [--shapes 256:15:4096:shared,256:15:4096:per,96:7:163840:shared,257:31:14336:shared]
                                   [--reps 3] [--warmup 1] [--distinct 8] [--host-b 64] [--host-shapes 1] [--out F]
+                                  [--space ell|stable]
 
 Workload (tests/batch_svm_reference.py: family): only the overlapping members with shift 0.2 (s = 1, 4, 7, ...; the
 separable ones end after a dozen iterations); `--distinct` of them, repeated to B.  `per`: every problem has its own
@@ -20,6 +21,10 @@ Per shape:
            live instance, one launch; an instance that has stopped receives a no-op cut, beta = +inf).  On the first
            --host-b instances of the first --host-shapes shapes, once.
 The three forms must agree bit for bit (niter, gamma, x_best) before a rate is printed; the tool checks it.
+
+--space stable runs the same three forms on EllStable spaces (include/ellhip_batch_stable_loops.h): the device loop on an
+EllStableBatch, tools/batch_svm_cpu.c over the CPU oracle's EllStable, and the host-driven form over ellhip_batch_update
+on an EllStableBatch (a stopped instance receives a cut that fails, beta = +inf).
 """
 from __future__ import annotations
 
@@ -41,6 +46,11 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 MAX_ITERS, TOL, KAPPA = 4000, 1e-6, 100.0
+STABLE = False  # --space stable
+
+
+def new_batch(pkg, B, n):
+    return (pkg.EllStableBatch if STABLE else pkg.EllBatch).new_with_scalar(np.full(B, KAPPA), np.zeros((B, n)), device=0)
 
 
 def bits(a):
@@ -74,7 +84,7 @@ def tiled(data, lab, B, shared):
 def device_run(pkg, data, lab):
     B, n = lab.shape[0], data.shape[-1] + 1
     prob = pkg.BatchSvmProblem(data, lab, device=0)
-    batch = pkg.EllBatch.new_with_scalar(np.full(B, KAPPA), np.zeros((B, n)), device=0)
+    batch = new_batch(pkg, B, n)
     t0 = time.perf_counter()
     x_best, has, niter, gamma, status = prob.optim(batch, math.inf, MAX_ITERS, TOL)
     return time.perf_counter() - t0, x_best, niter, gamma
@@ -95,7 +105,8 @@ def cpu_run(data, lab, shared):
                                "-Wl,-rpath," + odir, "-lm"])
         with open(fin, "wb") as f:
             f.write(struct.pack("<4qd", D, m, nfeat, MAX_ITERS, TOL) + full.tobytes() + lab.astype(np.int32).tobytes())
-        line = json.loads(subprocess.run([exe, fin, fout], check=True, capture_output=True, text=True).stdout)
+        line = json.loads(subprocess.run([exe, fin, fout] + (["stable"] if STABLE else []), check=True, capture_output=True,
+                                         text=True).stdout)
         raw = np.fromfile(fout, dtype=np.float64).reshape(D, nfeat + 3)
     return line, raw[:, 0].copy().view(np.int64), raw[:, 1].copy(), raw[:, 2:].copy()
 
@@ -103,7 +114,7 @@ def cpu_run(data, lab, shared):
 def host_run(pkg, svm, data, lab):
     """the form that needs no device loop: a host oracle per instance, ellhip_batch_update with K = 1 per iteration"""
     B, n = lab.shape[0], data.shape[-1] + 1
-    batch = pkg.EllBatch.new_with_scalar(np.full(B, KAPPA), np.zeros((B, n)), device=0)
+    batch = new_batch(pkg, B, n)
     gamma = np.full(B, math.inf)
     x_best = np.zeros((B, n))
     niter = np.full(B, MAX_ITERS, dtype=np.int64)
@@ -154,7 +165,7 @@ def bench(pkg, ref, svm, m, nfeat, B, shared, args, with_host):
     assert np.array_equal(bits(x_best), bits(c_x[which])), "device and CPU disagree (x_best)"
     rounds = rounds_of(niter)
     med = statistics.median(times)
-    out = {"m": m, "nfeat": nfeat, "n": nfeat + 1, "B": B, "table": "shared" if shared else "per-problem", "distinct": D,
+    out = {"space": "stable" if STABLE else "ell", "m": m, "nfeat": nfeat, "n": nfeat + 1, "B": B, "table": "shared" if shared else "per-problem", "distinct": D,
            "niter_min": int(niter.min()), "niter_max": int(niter.max()), "rounds": rounds,
            "table_bytes_per_iter": m * nfeat * 8,
            "device_s": {"median": med, "min": min(times), "max": max(times), "reps": args.reps},
@@ -181,7 +192,10 @@ def main():
     ap.add_argument("--host-b", type=int, default=64)
     ap.add_argument("--host-shapes", type=int, default=1)
     ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
+    ap.add_argument("--space", choices=("ell", "stable"), default="ell")
     args = ap.parse_args()
+    global STABLE
+    STABLE = args.space == "stable"
     import ellalgo_rs_amd as pkg
     import batch_svm_reference as ref
     import svm_reference as svm

@@ -7,7 +7,9 @@
  * int32 labels[B][m].  Every problem starts from Ell::new_with_scalar(100, 0) with gamma = +inf.
  * Output file: per problem int64 niter, double gamma, double x_best[nfeat + 1].
  *
- * Usage: batch_svm_cpu in.bin out.bin       prints one JSON line */
+ * Usage: batch_svm_cpu in.bin out.bin [stable]      prints one JSON line
+ * stable: the search space is the oracle's EllStable (orc_ellstable_update, a restatement of EllStable::update_core),
+ * from EllStable::new_with_scalar(100, 0). */
 #include <math.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -24,10 +26,11 @@ static double now(void) {
 }
 
 int main(int argc, char **argv) {
-    if (argc != 3) {
-        fprintf(stderr, "usage: %s in.bin out.bin\n", argv[0]);
+    if (argc != 3 && !(argc == 4 && !strcmp(argv[3], "stable"))) {
+        fprintf(stderr, "usage: %s in.bin out.bin [stable]\n", argv[0]);
         return 2;
     }
+    const int stable = argc == 4;
     FILE *f = fopen(argv[1], "rb");
     int64_t head[4];
     double tol;
@@ -47,13 +50,14 @@ int main(int argc, char **argv) {
     for (int64_t b = 0; b < B; ++b) {
         const double *d = data + b * m * nfeat;
         const int32_t *lab = labels + b * m;
-        orc_ell *space = orc_ell_new(n, 100.0, NULL, NULL, NULL);
+        orc_ell *space = stable ? NULL : orc_ell_new(n, 100.0, NULL, NULL, NULL);
+        orc_ellstable *sspace = stable ? orc_ellstable_new(n, 100.0, NULL, NULL, NULL) : NULL;
         double gamma = INFINITY;
         int64_t niter = max_iters;
         memset(xbest, 0, (size_t)n * sizeof(double));
         const double t0 = now();
         for (int64_t it = 0; it < max_iters; ++it) {
-            const double *x = orc_ell_xc(space);
+            const double *x = stable ? orc_ellstable_xc(sspace) : orc_ell_xc(space);
             double min_val = INFINITY; /*                                   svm_oracle.rs:28-40 */
             int64_t min_idx = 0;
             for (int64_t i = 0; i < m; ++i) {
@@ -78,9 +82,9 @@ int main(int argc, char **argv) {
                 gamma = min_val;
             }
             memcpy(xbest, x, (size_t)n * sizeof(double)); /*                cutting_plane.rs:303 */
-            const int status = orc_ell_update(space, 1, g, beta, 0, 0.0);
+            const int status = stable ? orc_ellstable_update(sspace, 1, g, beta, 0, 0.0) : orc_ell_update(space, 1, g, beta, 0, 0.0);
             rounds += 1;
-            if (status != 0 || orc_ell_tsq(space) < tol) { /*               :308 */
+            if (status != 0 || (stable ? orc_ellstable_tsq(sspace) : orc_ell_tsq(space)) < tol) { /* :308 */
                 niter = it;
                 break;
             }
@@ -89,7 +93,8 @@ int main(int argc, char **argv) {
         fwrite(&niter, sizeof niter, 1, out);
         fwrite(&gamma, sizeof gamma, 1, out);
         fwrite(xbest, sizeof(double), (size_t)n, out);
-        orc_ell_free(space);
+        if (stable) orc_ellstable_free(sspace);
+        else orc_ell_free(space);
     }
     fclose(out);
     printf("{\"B\": %lld, \"m\": %lld, \"nfeat\": %lld, \"rounds\": %lld, \"seconds\": %.6f, \"iters_per_s\": %.6g}\n",

@@ -4,15 +4,17 @@
 // thread 0 of every workgroup before the oracle, between the oracle and the update, and after the update; each of
 // these points follows a barrier, so thread 0's clock is the workgroup's.  The oracle and the update themselves are the
 // product's device functions.  Problems: random strictly feasible pencils of the requested shape (F_jk symmetric normal,
-// B_j = M M' + m I, c normal), Ell::new_with_scalar(10, 0).
+// B_j = M M' + m I, c normal), Ell::new_with_scalar(10, 0); with `stable` EllStable::new_with_scalar(10, 0) and the
+// row-parallel update of batch_stable_apply.hpp, launched as the _stable entry points launch it.
 //
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -o batch_lmi_split batch_lmi_split.hip
-//   ./batch_lmi_split n m J B tol        -> one JSON line: ns per round in the oracle and in the update
+//   ./batch_lmi_split n m J B tol [stable]   -> one JSON line: ns per round in the oracle and in the update
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <random>
 #include <vector>
 
@@ -29,7 +31,7 @@ using namespace ellhip;
         }                                                                               \
     } while (0)
 
-template <int T>
+template <int T, bool STABLE>
 __global__ __launch_bounds__(T) void k_loop_clocked(BatchParams P, BatchLmiParams L, BatchLmiLoop R, double* Q, double* xc,
                                                     double* kappa, const double* pencil, const double* matb,
                                                     const double* cvec, double* state /* [B][4]: gamma idx niter stopped */,
@@ -41,12 +43,11 @@ __global__ __launch_bounds__(T) void k_loop_clocked(BatchParams P, BatchLmiParam
     const long long b = (long long)blockIdx.x * P.epw + e;
     const bool active = e < P.epw && b < P.B;
     if (!__syncthreads_or(active && state[b * 4 + 3] == 0.0)) return;
-    const size_t per = batch_lds_doubles(n), lper = batch_lmi_lds_doubles(n, L.mmax);
+    const size_t per = batch_space_lds_doubles<STABLE>(n), lper = batch_lmi_lds_doubles(n, L.mmax);
     const int el = e < P.epw ? e : 0;
     double* q = sm + (size_t)el * per;
     double* g = q + (size_t)n * pitch;
-    double* gt = g + n;
-    double* sc = gt + n;
+    double* sc = q + batch_space_scalars_at<STABLE>(n);
     double* lx = sm + (size_t)P.epw * per + (size_t)el * lper;
     double* cl = lx + n;
     double* fa = cl + n;
@@ -73,9 +74,7 @@ __global__ __launch_bounds__(T) void k_loop_clocked(BatchParams P, BatchLmiParam
     __syncthreads();
     const bool lane_ok = tid < P.epw && b_first + tid < P.B;
     const int es = tid < P.epw ? tid : 0;
-    const double* g_s = sm + (size_t)es * per + (size_t)n * pitch;
-    const double* gt_s = g_s + n;
-    double* sc_s = const_cast<double*>(gt_s) + n;
+    double* q_s = sm + (size_t)es * per;
     const double* osc_s = sm + (size_t)P.epw * per + (size_t)es * lper + 2 * (size_t)n + (size_t)L.mmax * L.pm + L.mmax;
     const double* F = pencil + (active ? b : 0) * (long long)L.fstride;
     const double* Bm = matb + (active ? b : 0) * (long long)L.bstride;
@@ -91,8 +90,8 @@ __global__ __launch_bounds__(T) void k_loop_clocked(BatchParams P, BatchLmiParam
         const long long t1 = wall_clock64();
         const bool lane = lane_ok && osc_s[LO_STOPPED] == 0.0;
         const int kind = (lane && osc_s[LO_STATION] == shrunk_station) ? CUT_CENTRAL : CUT_BIAS;
-        batch_cut_apply(P, calc, live, i, q, g, gt, sc, xci, lane, g_s, gt_s, sc_s, kind, lane ? osc_s[LO_BETA] : 0.0, 0, 0.0,
-                        [](int, double) {});
+        batch_space_cut_apply<STABLE>(P, calc, live, i, q, xci, lane, q_s, kind, lane ? osc_s[LO_BETA] : 0.0, 0, 0.0,
+                                      [](int, double) {});
         const long long t2 = wall_clock64();
         t_oracle += t1 - t0;
         t_update += t2 - t1;
@@ -123,6 +122,7 @@ int main(int argc, char** argv) {
     const int n = argc > 1 ? atoi(argv[1]) : 16, m = argc > 2 ? atoi(argv[2]) : 12, J = argc > 3 ? atoi(argv[3]) : 3;
     const long long B = argc > 4 ? atoll(argv[4]) : 1024;
     const double tol = argc > 5 ? atof(argv[5]) : 1e-8;
+    const bool stable = argc > 6 && !strcmp(argv[6], "stable");
     if (n < 1 || n > BATCH_NMAX || m < 1 || m > BATCH_LMI_MMAX || J < 1 || J > BATCH_LMI_JMAX || B < 1) return 2;
     BatchLmiParams L{};
     L.J = J;
@@ -140,9 +140,10 @@ int main(int argc, char** argv) {
     // the batch engine's shape for n (batch_shape in batch_capi.inc.hpp)
     const int T = n <= 64 ? 256 : 128;
     int epw = std::min(64, T / n);
-    const size_t per_bytes = batch_lds_doubles(n) * sizeof(double);
+    const size_t space_doubles = stable ? batch_stable_apply_lds_doubles(n) : batch_lds_doubles(n);
+    const size_t per_bytes = space_doubles * sizeof(double);
     while (epw > 1 && (size_t)epw * per_bytes > 64 * 1024) epw -= 1;
-    const size_t lds = (size_t)epw * (batch_lds_doubles(n) + batch_lmi_lds_doubles(n, m)) * sizeof(double);
+    const size_t lds = (size_t)epw * (space_doubles + batch_lmi_lds_doubles(n, m)) * sizeof(double);
     if (lds > 159 * 1024) return 3;
     std::mt19937_64 rng(7);
     std::normal_distribution<double> nd;
@@ -194,13 +195,11 @@ int main(int argc, char** argv) {
     BatchParams P{B, n, batch_pitch(n), epw, 0, 0};
     BatchLmiLoop R{256, 0, 2000, tol};
     const EllCalcDev calc = EllCalcDev::make(n, 1);
-    if (T == 256) CHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_loop_clocked<256>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    else CHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_loop_clocked<128>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    auto kernel = T == 256 ? (stable ? &k_loop_clocked<256, true> : &k_loop_clocked<256, false>)
+                           : (stable ? &k_loop_clocked<128, true> : &k_loop_clocked<128, false>);
+    CHK(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     for (int launch = 0; launch < 8; ++launch) {  // 8 x 256 >= max_iters; a workgroup whose instances have stopped leaves at once
-        if (T == 256)
-            hipLaunchKernelGGL(k_loop_clocked<256>, dim3(grid), dim3(256), lds, 0, P, L, R, d_Q, d_xc, d_kap, d_pk, d_pb, d_c, d_state, d_clk, calc);
-        else
-            hipLaunchKernelGGL(k_loop_clocked<128>, dim3(grid), dim3(128), lds, 0, P, L, R, d_Q, d_xc, d_kap, d_pk, d_pb, d_c, d_state, d_clk, calc);
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(T), lds, 0, P, L, R, d_Q, d_xc, d_kap, d_pk, d_pb, d_c, d_state, d_clk, calc);
         CHK(hipGetLastError());
         CHK(hipDeviceSynchronize());
     }
@@ -221,10 +220,10 @@ int main(int argc, char** argv) {
         stopped += state[b * 4 + 3] != 0.0;
     }
     const double tick_ns = 10.0;  // wall_clock64: 100 MHz
-    printf("{\"probe\": \"batch_lmi_split\", \"n\": %d, \"m\": %d, \"J\": %d, \"B\": %lld, \"epw\": %d, \"threads\": %d, \"lds_bytes\": %zu, "
+    printf("{\"probe\": \"batch_lmi_split\", \"space\": \"%s\", \"n\": %d, \"m\": %d, \"J\": %d, \"B\": %lld, \"epw\": %d, \"threads\": %d, \"lds_bytes\": %zu, "
            "\"workgroup_rounds\": %lld, \"oracle_ns_per_round\": %.1f, \"update_ns_per_round\": %.1f, \"oracle_share\": %.3f, "
            "\"niter_min\": %.0f, \"niter_max\": %.0f, \"stopped\": %lld}\n",
-           n, m, J, B, epw, T, lds, rounds, tick_ns * t_or / rounds, tick_ns * t_up / rounds, (double)t_or / (double)(t_or + t_up),
+           stable ? "stable" : "ell", n, m, J, B, epw, T, lds, rounds, tick_ns * t_or / rounds, tick_ns * t_up / rounds, (double)t_or / (double)(t_or + t_up),
            nit_min, nit_max, stopped);
     return 0;
 }
