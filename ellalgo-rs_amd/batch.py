@@ -140,3 +140,16 @@ class EllStableBatch(_Batch):
     scratch), exactly as `EllStable.mq` and the oracle hold it."""
     _create = "ellhip_batch_create_stable"
     _from_space = "ellhip_batch_stable_from_space"
+
+
+class EllBatchStreamed(EllBatch):
+    """B `Ell` spaces of one dimension n <= 1024 with the matrices streamed from HBM (include/ellhip_batch_streamed.h):
+    the same calls and the same bits as `EllBatch`, past its n = 128.  The batched cutting-plane loops refuse it."""
+    _create = "ellhip_batch_create_streamed"
+    _from_space = "ellhip_batch_streamed_from_space"
+
+    @property
+    def is_streamed(self) -> bool:
+        v = int(self._lib.ellhip_batch_is_streamed(self._h))
+        capi.check(min(v, 0), "ellhip_batch_is_streamed")
+        return bool(v)

@@ -4,6 +4,7 @@
 
 #include "batch_kernels.hpp"
 #include "batch_stable_kernels.hpp"
+#include "batch_streamed_kernels.hpp"
 
 struct ellhip_batch {
     int device = 0;
@@ -15,6 +16,8 @@ struct ellhip_batch {
     size_t lds_bytes = 0;
     int no_defer_trick = 0;
     int use_parallel_cut = 1;
+    int streamed = 0;      // made by ellhip_batch_create_streamed / _streamed_from_space: k_batch_streamed_update, Q stays in HBM
+    int* d_sym = nullptr;  // streamed only: [B], 1 = that matrix is symmetric to the bit (batch_streamed_kernels.hpp)
     double* d_Q = nullptr;
     double* d_xc = nullptr;
     double* d_kappa = nullptr;
@@ -59,7 +62,13 @@ int batch_shape_stable(ellhip_batch* h) {
     return 0;
 }
 
+// batch_streamed_capi.inc.hpp
+int batch_streamed_shape(ellhip_batch* h);
+int batch_streamed_launch(ellhip_batch* h, long long K, const int* kinds, const double* grads, const double* b0, const int* hb1,
+                          const double* b1, int* status, double* tsq_out);
+
 int batch_shape(ellhip_batch* h) {
+    if (h->streamed) return batch_streamed_shape(h);
     if (h->variant == ELLHIP_SPACE_ELL_STABLE) return batch_shape_stable(h);
     h->T = h->n <= 64 ? 256 : 128;
     if (g_defaults.batch_threads > 0) h->T = g_defaults.batch_threads;  // ELLHIP_OPT_BATCH_THREADS
@@ -98,6 +107,7 @@ int batch_shape(ellhip_batch* h) {
 
 int batch_launch(ellhip_batch* h, long long K, const int* kinds, const double* grads, const double* b0, const int* hb1,
                  const double* b1, int* status, double* tsq_out) {
+    if (h->streamed) return batch_streamed_launch(h, K, kinds, grads, b0, hb1, b1, status, tsq_out);
     BatchParams P;
     P.B = h->B;
     P.n = h->n;
@@ -124,10 +134,15 @@ int batch_launch(ellhip_batch* h, long long K, const int* kinds, const double* g
     return 0;
 }
 
-int batch_new(ellhip_batch** out, long long B, long long n, int device, int variant) {
+int batch_new(ellhip_batch** out, long long B, long long n, int device, int variant, bool streamed = false) {
     if (!out) return fail(ELLHIP_E_INVALID, "out is NULL");
     *out = nullptr;
-    if (B < 1 || n < 1 || n > BATCH_NMAX) return fail(ELLHIP_E_INVALID, "batched engine: need B >= 1 and 1 <= n <= 128");
+    if (streamed) {
+        if (B < 1 || n < 1 || n > BATCH_STREAMED_NMAX)
+            return fail(ELLHIP_E_INVALID, "streamed batch engine: need B >= 1 and 1 <= n <= 1024");
+    } else if (B < 1 || n < 1 || n > BATCH_NMAX) {
+        return fail(ELLHIP_E_INVALID, "batched engine: need B >= 1 and 1 <= n <= 128");
+    }
     if ((double)B * (double)n * (double)n * 8.0 > 200e9) return fail(ELLHIP_E_NOMEM, "batched engine: B*n*n too large");
     const int ndev = ellhip_device_count();
     if (ndev <= 0) return fail(ELLHIP_E_NODEVICE, "no HIP device: the batched engine has no CPU path");
@@ -137,11 +152,14 @@ int batch_new(ellhip_batch** out, long long B, long long n, int device, int vari
     if (!h) return fail(ELLHIP_E_NOMEM, "host allocation failed");
     h->device = device;
     h->variant = variant;
+    h->streamed = streamed ? 1 : 0;
     h->B = B;
     h->n = (int)n;
     DeviceGuard guard(device);
     int rc = batch_shape(h);
     if (!rc) rc = batch_alloc(h);
+    if (!rc && streamed && hipMalloc(&h->d_sym, (size_t)B * sizeof(int)) != hipSuccess)
+        rc = fail(ELLHIP_E_NOMEM, "streamed batch engine: flags");
     if (rc) {
         ellhip_batch_destroy(h);
         return rc;
@@ -151,9 +169,9 @@ int batch_new(ellhip_batch** out, long long B, long long n, int device, int vari
 }
 
 int batch_create(ellhip_batch** out, int64_t B, int64_t n, const double* kappa, const double* mq, const double* diag,
-                 const double* xc, int device, int variant) {
+                 const double* xc, int device, int variant, bool streamed = false) {
     ellhip_batch* h = nullptr;
-    int rc = batch_new(&h, B, n, device, variant);
+    int rc = batch_new(&h, B, n, device, variant, streamed);
     if (rc) return rc;
     DeviceGuard guard(h->device);
     auto bail = [&](int code) {
@@ -194,14 +212,14 @@ int batch_create(ellhip_batch** out, int64_t B, int64_t n, const double* kappa, 
 }
 
 // B clones of one unsharded space: its buffer as ellhip_get_mq returns it, xc, kappa and tsq.
-int batch_clone_space(ellhip_batch** out, ellhip_space* s, int64_t B) {
+int batch_clone_space(ellhip_batch** out, ellhip_space* s, int64_t B, bool streamed = false) {
     DeviceGuard guard(s->device);
     int rc = make_q_current(s);  // recorded (deferred) shrinks / EllStable's mirrored layout belong to the buffer that is cloned
     if (rc) return rc;
     rc = read_back(s);
     if (rc) return rc;
     ellhip_batch* h = nullptr;
-    rc = batch_new(&h, B, s->n, s->device, s->variant);
+    rc = batch_new(&h, B, s->n, s->device, s->variant, streamed);
     if (rc) return rc;
     h->no_defer_trick = s->variant == ELLHIP_SPACE_ELL ? s->no_defer_trick : 0;
     h->use_parallel_cut = s->use_parallel_cut;
@@ -274,6 +292,7 @@ void ellhip_batch_destroy(ellhip_batch* h) {
     if (h->d_xc) (void)hipFree(h->d_xc);
     if (h->d_kappa) (void)hipFree(h->d_kappa);
     if (h->d_tsq) (void)hipFree(h->d_tsq);
+    if (h->d_sym) (void)hipFree(h->d_sym);
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
 }

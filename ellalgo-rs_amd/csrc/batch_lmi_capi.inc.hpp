@@ -76,6 +76,8 @@ BatchLoopShape batch_loop_shape(const ellhip_batch* s, bool stable) {
 // the handle's variant against the entry point's: the plain entry points take Ell handles, the _stable ones EllStable
 int batch_loop_check(const ellhip_batch* s, bool stable, const char* what) {
     const int want = stable ? ELLHIP_SPACE_ELL_STABLE : ELLHIP_SPACE_ELL;
+    if (s->streamed)  // the loops' kernels keep the matrix in LDS (include/ellhip_batch_streamed.h)
+        return fail(ELLHIP_E_INVALID, (std::string(what) + ": streamed batch handles are not supported").c_str());
     if (s->variant == want) return 0;
     const std::string msg = std::string(what) + (stable ? ": the _stable entry points take EllStable batch handles only"
                                                         : ": EllStable batch handles are not supported");

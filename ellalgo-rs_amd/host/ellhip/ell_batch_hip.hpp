@@ -3,18 +3,23 @@
 // `update_bias_cut(cuts)` is `for b in 0..B { space[b].update_bias_cut(&cuts[b]) }` in one launch, bit-identical to
 // the CPU arithmetic.  `from_space` makes B clones of one EllHip (BSearchAdaptor's clone per probe,
 // src/cutting_plane.rs:410).  EllStableBatchHip is the same for a `Vec<EllStable>` (clones of one EllStableHip).
+// EllBatchStreamedHip is a `Vec<Ell>` of one dimension n <= 1024 on the streamed engine (include/ellhip_batch_streamed.h):
+// the same calls and the same bits, the matrices streamed from HBM instead of held in LDS.
 #pragma once
 
 #include <cstdint>
 #include <vector>
 
 #include "../../../include/ellhip_batch.h"
+#include "../../../include/ellhip_batch_streamed.h"
 #include "ell_hip.hpp"
 
 namespace ellhip {
 
-template <int VARIANT>
+template <int VARIANT, bool STREAMED = false>
 class BatchHip {
+    static_assert(!STREAMED || VARIANT == ELLHIP_SPACE_ELL, "the streamed engine holds Ell spaces only");
+
   public:
     // Ell::new_with_scalar(val[b], xc[b]) for every b (src/ell.rs:71-73; EllStable: src/ell_stable.rs:33-35)
     static BatchHip new_with_scalar(const Arr& val, const std::vector<Arr>& xc, int device = -1) {
@@ -32,7 +37,9 @@ class BatchHip {
     template <int SPACE>
     static BatchHip from_space(SpaceHip<SPACE>& space, std::size_t B) {
         BatchHip r;
-        if (VARIANT == ELLHIP_SPACE_ELL_STABLE)
+        if (STREAMED)
+            check(ellhip_batch_streamed_from_space(&r.h_, space.handle(), (int64_t)B), "ellhip_batch_streamed_from_space");
+        else if (VARIANT == ELLHIP_SPACE_ELL_STABLE)
             check(ellhip_batch_stable_from_space(&r.h_, space.handle(), (int64_t)B), "ellhip_batch_stable_from_space");
         else
             check(ellhip_batch_from_space(&r.h_, space.handle(), (int64_t)B), "ellhip_batch_from_space");
@@ -87,6 +94,7 @@ class BatchHip {
         check(ellhip_batch_set_no_defer_trick(h_, f ? 1 : 0), "set_no_defer_trick");
     }
     void set_use_parallel_cut(bool f) { check(ellhip_batch_set_use_parallel_cut(h_, f ? 1 : 0), "set_use_parallel_cut"); }
+    bool is_streamed() const { return check(ellhip_batch_is_streamed(h_), "ellhip_batch_is_streamed") == 1; }
     ellhip_batch* handle() { return h_; }
 
   private:
@@ -100,10 +108,10 @@ class BatchHip {
         if (mq) fm = flatten(*mq, n_ * n_);
         if (diag) fd = flatten(*diag, n_);
         const bool stable = VARIANT == ELLHIP_SPACE_ELL_STABLE;
-        check((stable ? ellhip_batch_create_stable : ellhip_batch_create)(
+        check((STREAMED ? ellhip_batch_create_streamed : stable ? ellhip_batch_create_stable : ellhip_batch_create)(
                   &h_, (int64_t)B_, (int64_t)n_, kappa ? kappa->data() : nullptr, mq ? fm.data() : nullptr,
                   diag ? fd.data() : nullptr, fx.data(), device),
-              stable ? "ellhip_batch_create_stable" : "ellhip_batch_create");
+              STREAMED ? "ellhip_batch_create_streamed" : stable ? "ellhip_batch_create_stable" : "ellhip_batch_create");
     }
     Arr flatten(const std::vector<Arr>& v, std::size_t each) const {
         if (v.size() != B_) throw Error(ELLHIP_E_INVALID, "need one entry per ellipsoid");
@@ -149,5 +157,6 @@ class BatchHip {
 // a `Vec<Ell>` / a `Vec<EllStable>` behind one handle
 using EllBatchHip = BatchHip<ELLHIP_SPACE_ELL>;
 using EllStableBatchHip = BatchHip<ELLHIP_SPACE_ELL_STABLE>;
+using EllBatchStreamedHip = BatchHip<ELLHIP_SPACE_ELL, true>;
 
 }  // namespace ellhip
