@@ -71,7 +71,7 @@ __device__ __forceinline__ void batch_copy(double* __restrict__ sm, double* __re
 // local ellipsoid e (q, g, gt, sc are that ellipsoid's LDS blocks, xci its xc[i]); `scalar_lane` t of wave 0 runs the scalar
 // stage for local ellipsoid t (g_s, gt_s, sc_s; kind_k, b0_k, hb1_k, b1_k: that ellipsoid's cut) and hands its status and
 // tsq to `emit`.  The caller has stored g and synchronised; the function ends with a barrier.  Shared by k_batch_update
-// and k_batch_lmi_loop (batch_lmi_kernels.hpp), so both apply a cut with the same instructions.
+// and k_batch_loop (batch_loop_kernels.hpp), so both apply a cut with the same instructions.
 template <class Emit>
 __device__ __forceinline__ void batch_cut_apply(const BatchParams& P, const EllCalcDev& calc, const bool active, const int i,
                                                 double* q, const double* g, double* gt, double* sc, double& xci,

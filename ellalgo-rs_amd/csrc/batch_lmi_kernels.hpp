@@ -1,8 +1,7 @@
-// batch_lmi_kernels.hpp -- B independent LMI-constrained cutting-plane solves, oracle and ellipsoid update in one kernel
-// (include/ellhip_batch_lmi.h).
+// batch_lmi_kernels.hpp -- the oracle of B independent LMI-constrained cutting-plane solves, as a policy of the loop kernel
+// (include/ellhip_batch_lmi.h; the loop itself: batch_loop_kernels.hpp).
 //
-// A workgroup owns the ellipsoids the batch engine gives it (batch_kernels.hpp: thread (e, i) = row i of local
-// ellipsoid e, Q in LDS) and, for each of them, runs up to `iters` rounds of
+// For every ellipsoid of its workgroup k_batch_loop<T, STABLE, BatchLmiOracle> runs rounds of
 //     oracle (round-robin over J LMI blocks and the objective, tests/lmi_tests.rs:142-171)
 //  -> scalar stage + rank-1 (batch_cut_apply, the same code k_batch_update runs)
 // without leaving the kernel.  Everything is + - * / in the reference's fold order, so the loop is bit-identical to
@@ -21,11 +20,11 @@
 // doubles and a thread of F(x) walks n consecutive doubles; B[inst][block][a][b].
 //
 // Barriers are workgroup-wide, so the walk over stations runs in lockstep: every instance of the workgroup takes its
-// next station in the same step, and the column loop runs to the largest block size.  Every loop is bounded by iters,
-// J + 1, M and n; no thread waits on another workgroup.
+// next station in the same step, and the column loop runs to the largest block size.  Every loop is bounded by J + 1, M
+// and n; no thread waits on another workgroup.
 #pragma once
 
-#include "batch_stable_apply.hpp"
+#include "batch_loop_kernels.hpp"
 
 namespace ellhip {
 
@@ -51,18 +50,14 @@ __host__ __device__ inline size_t batch_lmi_lds_doubles(int n, int mmax) {
     return (2 * (size_t)n + (size_t)mmax * (size_t)(mmax | 1) + (size_t)mmax + 16) | 1;
 }
 
-// oracle scalars (LDS, per instance)
+// oracle scalars (LDS, per instance), after the loop's own (batch_loop_kernels.hpp)
 enum : int {
-    LO_GAMMA = 0,    // best-so-far objective value
-    LO_IDX = 1,      // round-robin index
-    LO_F0 = 2,       // c . x
-    LO_BETA = 3,     // the cut's beta
-    LO_STATION = 4,  // -1 while walking; the station that cut; nstation = every station passed
-    LO_CUR = 5,      // block under factorisation in this step, -1 = none
-    LO_NITER = 8,
-    LO_STOPPED = 9,
-    LO_HASBEST = 10,
-    LO_STATUS = 11,
+    LO_GAMMA = BL_GAMMA,          // best-so-far objective value
+    LO_IDX = BL_SCALARS,          // round-robin index
+    LO_F0 = BL_SCALARS + 1,       // c . x
+    LO_BETA = BL_SCALARS + 2,     // the cut's beta
+    LO_STATION = BL_SCALARS + 3,  // -1 while walking; the station that cut; nstation = every station passed
+    LO_CUR = BL_SCALARS + 4,      // block under factorisation in this step, -1 = none
 };
 
 // The oracle for the workgroup's instances, collectively (it contains barriers: every thread of the workgroup calls it).
@@ -194,137 +189,63 @@ __device__ __forceinline__ void batch_lmi_oracle(const BatchLmiParams& L, const 
     __syncthreads();
 }
 
-struct BatchLmiLoop {
-    int iters;            // iterations this launch may run
-    int feas;             // 1: cutting_plane_feas
-    long long max_iters;
-    double tol;
+// The oracle as the loop kernel's policy (batch_loop_kernels.hpp).  Per instance in HBM: the pencil, the objective vector
+// and the round-robin index.
+struct BatchLmiOracle {
+    struct Args {
+        BatchLmiParams L;
+        const double* pencil;  // [B][block][a][b][k]
+        const double* matb;    // [B][block][a][b], or null
+        const double* cvec;    // [B][n], or null
+        int* idx;              // [B]
+    };
+    struct Regs {
+        const double *F, *Bm;  // this instance's pencil
+    };
+    struct Lds {
+        double *x, *cl, *fa, *wit, *osc;
+    };
+    static __host__ __device__ inline size_t lds_doubles(const Args& A, int n) { return batch_lmi_lds_doubles(n, A.L.mmax); }
+    static __device__ __forceinline__ size_t scalars_at(const Args& A, int n) {
+        return 2 * (size_t)n + (size_t)A.L.mmax * A.L.pm + A.L.mmax;
+    }
+    static __device__ __forceinline__ Lds carve(const Args& A, int n, double* blk) {
+        Lds d;
+        d.x = blk;
+        d.cl = d.x + n;
+        d.fa = d.cl + n;
+        d.wit = d.fa + (size_t)A.L.mmax * A.L.pm;
+        d.osc = d.wit + A.L.mmax;
+        return d;
+    }
+    static __device__ __forceinline__ void load(const Args& A, bool active, long long b, int i, int n, double* blk, Regs& r) {
+        const Lds d = carve(A, n, blk);
+        if (active) d.cl[i] = A.L.has_c ? A.cvec[b * n + i] : 0.0;
+        if (active && i == 0) d.osc[LO_IDX] = (double)A.idx[b];
+        r.F = A.pencil + (active ? b : 0) * (long long)A.L.fstride;
+        r.Bm = A.matb ? A.matb + (active ? b : 0) * (long long)A.L.bstride : nullptr;
+    }
+    static __device__ __forceinline__ void assess(const Args& A, const BatchLoopRun&, bool live, int i, int n, double xci,
+                                                  double* blk, Regs& r, double* g) {
+        const Lds d = carve(A, n, blk);
+        if (live) d.x[i] = xci;
+        __syncthreads();
+        batch_lmi_oracle(A.L, live, i, n, r.F, r.Bm, d.x, d.cl, d.fa, d.wit, d.osc, g);
+    }
+    // every station passed: cutting_plane_optim shrinks (tests/lmi_tests.rs:170), cutting_plane_feas has its point
+    static __device__ __forceinline__ BatchOutcome outcome(const Args& A, int feas, const double* osc) {
+        const bool all_pass = osc[LO_STATION] == (double)(A.L.J + 1);
+        return BatchOutcome{all_pass ? (feas ? BOUT_FEAS : BOUT_SHRUNK) : BOUT_CUT, osc[LO_BETA], 0, 0.0};
+    }
+    static __device__ __forceinline__ void store(const Args& A, long long b, const double* osc, const Regs&) {
+        A.idx[b] = (int)osc[LO_IDX];
+    }
 };
-
-// cutting_plane_optim (src/cutting_plane.rs:286-313) / cutting_plane_feas (:205-227) for every instance of the workgroup.
-// Loop state per instance lives in HBM between launches: idx, gamma, x_best, has_best, niter, stopped, status.
-// STABLE: the spaces are EllStable buffers and a cut is batch_stable_cut_apply (batch_stable_apply.hpp).
-template <int T, bool STABLE = false>
-__global__ __launch_bounds__(T) void k_batch_lmi_loop(BatchParams P, BatchLmiParams L, BatchLmiLoop R,
-                                                      double* __restrict__ Q, double* __restrict__ xc,
-                                                      double* __restrict__ kappa, double* __restrict__ tsq,
-                                                      const double* __restrict__ pencil, const double* __restrict__ matb,
-                                                      const double* __restrict__ cvec, int* __restrict__ idx_io,
-                                                      double* __restrict__ gamma_io, double* __restrict__ xbest,
-                                                      int* __restrict__ has_best, long long* __restrict__ niter_io,
-                                                      int* __restrict__ stopped_io, int* __restrict__ status_io,
-                                                      int* __restrict__ nstopped, EllCalcDev calc) {
-    extern __shared__ double sm[];
-    const int n = P.n, pitch = P.pitch;
-    const int tid = threadIdx.x;
-    const int e = tid / n, i = tid - e * n;
-    const long long b = (long long)blockIdx.x * P.epw + e;
-    const bool active = e < P.epw && b < P.B;
-    if (!__syncthreads_or(active && stopped_io[b] == 0)) return;  // all of this workgroup's instances have stopped
-
-    const size_t per = batch_space_lds_doubles<STABLE>(n);
-    const size_t lper = batch_lmi_lds_doubles(n, L.mmax);
-    const int el = e < P.epw ? e : 0;
-    double* q = sm + (size_t)el * per;
-    double* g = q + (size_t)n * pitch;
-    double* sc = q + batch_space_scalars_at<STABLE>(n);  // as in k_batch_update
-    double* lx = sm + (size_t)P.epw * per + (size_t)el * lper;
-    double* cl = lx + n;
-    double* fa = cl + n;
-    double* wit = fa + (size_t)L.mmax * L.pm;
-    double* osc = wit + L.mmax;
-
-    const long long b_first = (long long)blockIdx.x * P.epw;
-    const int nb = (int)((P.B - b_first < P.epw) ? P.B - b_first : P.epw);
-    double* Qwg = Q + b_first * (long long)n * n;
-    batch_copy<T, true>(sm, Qwg, nb * n * n, n, pitch, (int)per, tid);
-    double xci = 0.0, xb = 0.0;
-    if (active) {
-        xci = xc[b * n + i];
-        xb = xbest[b * n + i];
-        cl[i] = L.has_c ? cvec[b * n + i] : 0.0;
-    }
-    if (active && i == 0) {
-        sc[3] = (double)ST_SUCCESS;
-        sc[4] = kappa[b];
-        sc[5] = tsq[b];
-        osc[LO_GAMMA] = gamma_io[b];
-        osc[LO_IDX] = (double)idx_io[b];
-        osc[LO_NITER] = (double)niter_io[b];
-        osc[LO_STOPPED] = (double)stopped_io[b];
-        osc[LO_HASBEST] = (double)has_best[b];
-        osc[LO_STATUS] = (double)status_io[b];
-    }
-    __syncthreads();
-
-    const bool lane_ok = tid < P.epw && b_first + tid < P.B;
-    const int es = tid < P.epw ? tid : 0;
-    double* q_s = sm + (size_t)es * per;
-    const double* osc_s = sm + (size_t)P.epw * per + (size_t)es * lper + 2 * (size_t)n + (size_t)L.mmax * L.pm + L.mmax;
-    const double* F = pencil + (active ? b : 0) * (long long)L.fstride;
-    const double* Bm = matb ? matb + (active ? b : 0) * (long long)L.bstride : nullptr;
-    const double shrunk_station = (double)(L.J + 1);
-
-    for (int it = 0; it < R.iters; ++it) {
-        const bool live = active && osc[LO_STOPPED] == 0.0;
-        if (!__syncthreads_or(live)) break;
-        if (live) lx[i] = xci;
-        __syncthreads();
-        batch_lmi_oracle(L, live, i, n, F, Bm, lx, cl, fa, wit, osc, g);
-        const bool all_pass = live && osc[LO_STATION] == shrunk_station;
-        const bool found = R.feas && all_pass;  // cutting_plane_feas: a feasible point ends the loop   :217-220
-        if (all_pass) xb = xci;                 // x_best = Some(space.xc())                            :303
-        const bool upd = live && !found;
-        const bool lane = lane_ok && osc_s[LO_STOPPED] == 0.0 && !(R.feas && osc_s[LO_STATION] == shrunk_station);
-        const int kind = (lane && osc_s[LO_STATION] == shrunk_station) ? CUT_CENTRAL : CUT_BIAS;  // :301-307
-        const double beta = lane ? osc_s[LO_BETA] : 0.0;
-        batch_space_cut_apply<STABLE>(P, calc, upd, i, q, xci, lane, q_s, kind, beta, 0, 0.0, [](int, double) {});
-        if (live && i == 0) {
-            if (all_pass) osc[LO_HASBEST] = 1.0;
-            bool stop;
-            if (found) {
-                osc[LO_STATUS] = (double)ST_SUCCESS;
-                stop = true;
-            } else if (sc[3] != (double)ST_SUCCESS || sc[5] < R.tol) {  //                              :308 / :222
-                osc[LO_STATUS] = sc[3];
-                stop = true;
-            } else {
-                const double done = osc[LO_NITER] + 1.0;
-                osc[LO_NITER] = done;
-                osc[LO_STATUS] = (double)ST_SUCCESS;
-                stop = done >= (double)R.max_iters;
-            }
-            if (stop) {
-                osc[LO_STOPPED] = 1.0;
-                atomicAdd(nstopped, 1);
-            }
-        }
-        __syncthreads();
-    }
-
-    if (active) {
-        xc[b * n + i] = xci;
-        if (osc[LO_HASBEST] != 0.0) xbest[b * n + i] = xb;
-    }
-    if (active && i == 0) {
-        kappa[b] = sc[4];
-        tsq[b] = sc[5];
-        gamma_io[b] = osc[LO_GAMMA];
-        idx_io[b] = (int)osc[LO_IDX];
-        niter_io[b] = (long long)osc[LO_NITER];
-        stopped_io[b] = (int)osc[LO_STOPPED];
-        has_best[b] = (int)osc[LO_HASBEST];
-        status_io[b] = (int)osc[LO_STATUS];
-    }
-    batch_copy<T, false>(sm, Qwg, nb * n * n, n, pitch, (int)per, tid);
-}
 
 // One oracle call per instance at x[B][n]: the same device function, without an ellipsoid.
 template <int T>
-__global__ __launch_bounds__(T) void k_batch_lmi_assess(long long B, int n, int epw, BatchLmiParams L,
-                                                        const double* __restrict__ pencil, const double* __restrict__ matb,
-                                                        const double* __restrict__ cvec, const double* __restrict__ x,
-                                                        int* __restrict__ idx_io, double* __restrict__ gamma_io,
+__global__ __launch_bounds__(T) void k_batch_lmi_assess(long long B, int n, int epw, BatchLmiOracle::Args A,
+                                                        const double* __restrict__ x, double* __restrict__ gamma_io,
                                                         double* __restrict__ grad_out, double* __restrict__ beta_out,
                                                         int* __restrict__ station_out) {
     extern __shared__ double sm[];
@@ -332,32 +253,25 @@ __global__ __launch_bounds__(T) void k_batch_lmi_assess(long long B, int n, int 
     const int e = tid / n, i = tid - e * n;
     const long long b = (long long)blockIdx.x * epw + e;
     const bool active = e < epw && b < B;
-    const size_t lper = batch_lmi_lds_doubles(n, L.mmax) + (size_t)n;
-    double* lx = sm + (size_t)(e < epw ? e : 0) * lper;
-    double* cl = lx + n;
-    double* fa = cl + n;
-    double* wit = fa + (size_t)L.mmax * L.pm;
-    double* osc = wit + L.mmax;
-    double* g = osc + 16;
+    const size_t lper = batch_lmi_lds_doubles(n, A.L.mmax) + (size_t)n;
+    double* blk = sm + (size_t)(e < epw ? e : 0) * lper;
+    const BatchLmiOracle::Lds d = BatchLmiOracle::carve(A, n, blk);
+    double* g = d.osc + 16;
+    BatchLmiOracle::Regs r;
+    BatchLmiOracle::load(A, active, b, i, n, blk, r);
     if (active) {
-        lx[i] = x[b * n + i];
-        cl[i] = L.has_c ? cvec[b * n + i] : 0.0;
+        d.x[i] = x[b * n + i];
         g[i] = grad_out[b * n + i];
     }
-    if (active && i == 0) {
-        osc[LO_GAMMA] = gamma_io[b];
-        osc[LO_IDX] = (double)idx_io[b];
-    }
+    if (active && i == 0) d.osc[LO_GAMMA] = gamma_io[b];
     __syncthreads();
-    const double* F = pencil + (active ? b : 0) * (long long)L.fstride;
-    const double* Bm = matb ? matb + (active ? b : 0) * (long long)L.bstride : nullptr;
-    batch_lmi_oracle(L, active, i, n, F, Bm, lx, cl, fa, wit, osc, g);
+    batch_lmi_oracle(A.L, active, i, n, r.F, r.Bm, d.x, d.cl, d.fa, d.wit, d.osc, g);
     if (active) grad_out[b * n + i] = g[i];
     if (active && i == 0) {
-        gamma_io[b] = osc[LO_GAMMA];
-        idx_io[b] = (int)osc[LO_IDX];
-        beta_out[b] = osc[LO_BETA];
-        station_out[b] = (int)osc[LO_STATION];
+        gamma_io[b] = d.osc[LO_GAMMA];
+        BatchLmiOracle::store(A, b, d.osc, r);
+        beta_out[b] = d.osc[LO_BETA];
+        station_out[b] = (int)d.osc[LO_STATION];
     }
 }
 

@@ -1,0 +1,244 @@
+// batch_loop_capi.inc.hpp -- the host side the batched device-resident cutting-plane loops share: the loop state an oracle
+// handle owns, the launch shapes and the one driver that runs k_batch_loop (batch_loop_kernels.hpp) over a batch handle.
+// Included at the end of ellhip_capi.hip, after batch_capi.inc.hpp (it drives the batch engine's handle directly) and
+// before batch_lmi_capi.inc.hpp, batch_lowpass_capi.inc.hpp and batch_svm_capi.inc.hpp.
+//
+// Reference: src/cutting_plane.rs:205-227, 286-313 (loops).
+#include "batch_loop_kernels.hpp"
+
+namespace {
+
+// The part of an oracle handle that every batched loop has: where the handle lives, its stream, and the loop state.
+struct BatchLoopBuffers {
+    int device = 0;
+    long long B = 0;
+    int n = 0;
+    int chunk = 256;               // iterations per launch
+    double* d_gamma = nullptr;     // [B]
+    double* d_xbest = nullptr;     // [B][n]
+    long long* d_niter = nullptr;  // [B]
+    int* d_ints = nullptr;         // has_best [B], stopped [B], status [B], nstopped [1]
+    hipStream_t stream = nullptr;
+};
+
+// the stream and the buffers, zeroed
+hipError_t batch_loop_alloc(BatchLoopBuffers& st, int device, long long B, int n) {
+    st.device = device;
+    st.B = B;
+    st.n = n;
+    const size_t sB = (size_t)B, sn = (size_t)n;
+    hipError_t e = hipStreamCreateWithFlags(&st.stream, hipStreamNonBlocking);
+    if (e == hipSuccess) e = hipMalloc(&st.d_gamma, sB * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc(&st.d_xbest, sB * sn * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc(&st.d_niter, sB * sizeof(long long));
+    if (e == hipSuccess) e = hipMalloc(&st.d_ints, (3 * sB + 1) * sizeof(int));
+    if (e == hipSuccess) e = fill_now(st.d_gamma, 0, sB * sizeof(double), st.stream);
+    if (e == hipSuccess) e = fill_now(st.d_xbest, 0, sB * sn * sizeof(double), st.stream);
+    if (e == hipSuccess) e = fill_now(st.d_niter, 0, sB * sizeof(long long), st.stream);
+    if (e == hipSuccess) e = fill_now(st.d_ints, 0, (3 * sB + 1) * sizeof(int), st.stream);
+    return e;
+}
+
+// a new solve: nobody has stopped, nobody has a best point, no iteration done (x_best rows are only read where has_best)
+hipError_t batch_loop_reset(BatchLoopBuffers& st, hipStream_t stream) {
+    const size_t sB = (size_t)st.B;
+    const hipError_t e = fill_now(st.d_ints, 0, (3 * sB + 1) * sizeof(int), stream);
+    return e == hipSuccess ? fill_now(st.d_niter, 0, sB * sizeof(long long), stream) : e;
+}
+
+// waits for the stream; the caller has selected the device
+void batch_loop_free(BatchLoopBuffers& st) {
+    if (st.stream) (void)hipStreamSynchronize(st.stream);
+    void* bufs[] = {st.d_gamma, st.d_xbest, st.d_niter, st.d_ints};
+    for (void* p : bufs)
+        if (p) (void)hipFree(p);
+    if (st.stream) (void)hipStreamDestroy(st.stream);
+    st = BatchLoopBuffers{};
+}
+
+BatchLoopState batch_loop_view(const BatchLoopBuffers& st) {
+    const size_t sB = (size_t)st.B;
+    BatchLoopState S;
+    S.gamma = st.d_gamma;
+    S.xbest = st.d_xbest;
+    S.has_best = st.d_ints;
+    S.niter = st.d_niter;
+    S.stopped = st.d_ints + sB;
+    S.status = st.d_ints + 2 * sB;
+    S.nstopped = st.d_ints + 3 * sB;
+    return S;
+}
+
+int batch_loop_set_chunk(BatchLoopBuffers* st, int64_t iters, const char* what) {
+    if (!st) return fail(ELLHIP_E_INVALID, "NULL handle");
+    if (iters < 1 || iters > 4096) return fail(ELLHIP_E_INVALID, (std::string(what) + ": chunk must be in 1..4096").c_str());
+    st->chunk = (int)iters;
+    return 0;
+}
+
+// 160 KiB per workgroup, less the 1 KiB kept for the kernel's static LDS (the barrier votes)
+constexpr size_t BATCH_LOOP_LDS_MAX = 159 * 1024;
+
+// more than the default 64 KiB of dynamic LDS needs an opt-in per kernel and per device; as in batch_shape it is only ever
+// raised, with the high-water marks kept per (oracle, device, block size)
+template <class Oracle>
+int batch_loop_allow_lds(const void* kernel, int device, int slot, size_t bytes) {
+    constexpr int MAXDEV = 64;
+    static std::atomic<int> granted[MAXDEV][6];  // T = 64, 128, 256 on Ell, then on EllStable
+    const bool known = device >= 0 && device < MAXDEV;
+    if (known && (int)bytes <= granted[device][slot].load()) return 0;
+    HIPCHK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    if (known) {
+        int seen = granted[device][slot].load();
+        while (seen < (int)bytes && !granted[device][slot].compare_exchange_weak(seen, (int)bytes)) {}
+    }
+    return 0;
+}
+
+// n threads per instance without a batch handle's own shape: 256 threads up to n = 64, else 128; at most 64 instances
+// (one wave runs the scalar stage, one lane per instance) and at most 64 KiB of `doubles` per instance
+struct BatchRowShape {
+    int T = 64, epw = 1;
+};
+BatchRowShape batch_row_shape(int n, size_t doubles) {
+    BatchRowShape r;
+    r.T = n <= 64 ? 256 : 128;
+    r.epw = std::min(64, r.T / n);
+    while (r.epw > 1 && (size_t)r.epw * doubles * sizeof(double) > 64 * 1024) r.epw -= 1;
+    return r;
+}
+
+// How the loop kernel is launched on a batch handle.  An Ell handle is launched as the batch engine shaped it.  An EllStable
+// handle is shaped for k_batch_update_stable's one lane per ellipsoid (one wave, up to 64 ellipsoids); the loop kernel
+// gives an instance n threads, so it takes batch_row_shape with batch_stable_apply_lds_doubles in it.  slot: the entry of
+// batch_loop_allow_lds's table.
+struct BatchLoopShape {
+    int T = 64, epw = 1, slot = 0;
+    size_t space_doubles = 0;  // LDS doubles of one instance's space
+};
+
+BatchLoopShape batch_loop_shape(const ellhip_batch* s, bool stable) {
+    BatchLoopShape sh;
+    if (!stable) {
+        sh.T = s->T;
+        sh.epw = s->epw;
+        sh.space_doubles = batch_lds_doubles(s->n);
+    } else {
+        sh.space_doubles = batch_stable_apply_lds_doubles(s->n);
+        const BatchRowShape r = batch_row_shape(s->n, sh.space_doubles);
+        sh.T = r.T;
+        sh.epw = r.epw;
+    }
+    sh.slot = (sh.T == 64 ? 0 : (sh.T == 128 ? 1 : 2)) + (stable ? 3 : 0);
+    return sh;
+}
+
+// the handle's variant against the entry point's: the plain entry points take Ell handles, the _stable ones EllStable
+int batch_loop_check(const ellhip_batch* s, bool stable, const char* what) {
+    const int want = stable ? ELLHIP_SPACE_ELL_STABLE : ELLHIP_SPACE_ELL;
+    if (s->streamed)  // the loop kernel keeps the matrix in LDS (include/ellhip_batch_streamed.h)
+        return fail(ELLHIP_E_INVALID, (std::string(what) + ": streamed batch handles are not supported").c_str());
+    if (s->variant == want) return 0;
+    const std::string msg = std::string(what) + (stable ? ": the _stable entry points take EllStable batch handles only"
+                                                        : ": EllStable batch handles are not supported");
+    return fail(ELLHIP_E_INVALID, msg.c_str());
+}
+
+BatchParams batch_loop_params(const ellhip_batch* s, const BatchLoopShape& sh) {
+    BatchParams P;
+    P.B = s->B;
+    P.n = s->n;
+    P.pitch = batch_pitch(s->n);
+    P.epw = sh.epw;
+    P.K = 0;
+    P.no_defer_trick = s->no_defer_trick;
+    return P;
+}
+
+template <int T, bool STABLE, class Oracle>
+int batch_loop_launch(const ellhip_batch* s, const BatchLoopShape& sh, size_t lds, const BatchParams& P, const BatchLoopRun& R,
+                      const BatchLoopState& S, const typename Oracle::Args& A, const EllCalcDev& calc) {
+    if (const int rc = batch_loop_allow_lds<Oracle>(reinterpret_cast<const void*>(&k_batch_loop<T, STABLE, Oracle>), s->device,
+                                                    sh.slot, lds))
+        return rc;
+    const unsigned grid = (unsigned)((s->B + sh.epw - 1) / sh.epw);
+    hipLaunchKernelGGL((k_batch_loop<T, STABLE, Oracle>), dim3(grid), dim3(T), lds, s->stream, P, R, s->d_Q, s->d_xc,
+                       s->d_kappa, s->d_tsq, S, A, calc);
+    return 0;
+}
+
+// What a refusal calls the loop, the shape and the dimension (the messages are the entry points' own).
+struct BatchLoopWords {
+    const char* what;   // "batched LMI loop"
+    const char* shape;  // "(n, m)": what decides the LDS an instance needs
+    const char* n_is;   // "" or how the oracle's n comes about
+};
+
+// cutting_plane_optim (feas = 0, gamma in and out) or cutting_plane_feas for every instance: up to max_iters rounds in
+// launches of st.chunk, until every instance has stopped.
+// stable: the spaces are EllStable (include/ellhip_batch_stable_loops.h).  The caller has checked its pointers.
+template <class Oracle>
+int batch_loop_run(ellhip_batch* s, BatchLoopBuffers& st, const typename Oracle::Args& A,
+                   const BatchLoopWords& w, bool stable, int feas, double* gamma_inout, int64_t max_iters, double tol,
+                   double* x_out, int32_t* has_out, int64_t* niter_out, int32_t* status_out) {
+    const std::string what(w.what);
+    if (const int rc = batch_loop_check(s, stable, w.what)) return rc;
+    if (s->B != st.B || s->n != st.n)
+        return fail(ELLHIP_E_INVALID, (what + ": spaces and oracle differ in B or n" + w.n_is).c_str());
+    if (s->device != st.device) return fail(ELLHIP_E_INVALID, (what + ": spaces and oracle live on different devices").c_str());
+    if (max_iters < 0) return fail(ELLHIP_E_INVALID, "max_iters must be >= 0");
+    const size_t B = (size_t)st.B, n = (size_t)st.n;
+    const BatchLoopShape sh = batch_loop_shape(s, stable);
+    const size_t lds = (size_t)sh.epw * (sh.space_doubles + Oracle::lds_doubles(A, s->n)) * sizeof(double);
+    if (lds > BATCH_LOOP_LDS_MAX)
+        return fail(ELLHIP_E_INVALID, (what + ": this " + w.shape + " needs more LDS than a workgroup has").c_str());
+    DeviceGuard guard(s->device);
+    const BatchLoopState S = batch_loop_view(st);
+    HIPCHK(hipStreamSynchronize(s->stream));
+    HIPCHK(hipStreamSynchronize(st.stream));
+    HIPCHK(batch_loop_reset(st, s->stream));
+    if (!feas) HIPCHK(hipMemcpy(st.d_gamma, gamma_inout, B * sizeof(double), hipMemcpyHostToDevice));
+    const BatchParams P = batch_loop_params(s, sh);
+    const EllCalcDev calc = EllCalcDev::make(s->n, s->use_parallel_cut);
+    BatchLoopRun R;
+    R.feas = feas;
+    R.max_iters = max_iters;
+    R.tol = tol;
+    for (long long done = 0; done < max_iters; done += st.chunk) {
+        R.iters = (int)std::min<long long>(st.chunk, max_iters - done);
+        int rc;
+        if (stable) {
+            rc = sh.T == 128 ? batch_loop_launch<128, true, Oracle>(s, sh, lds, P, R, S, A, calc)
+                             : batch_loop_launch<256, true, Oracle>(s, sh, lds, P, R, S, A, calc);
+        } else {
+            rc = sh.T == 64    ? batch_loop_launch<64, false, Oracle>(s, sh, lds, P, R, S, A, calc)
+                 : sh.T == 128 ? batch_loop_launch<128, false, Oracle>(s, sh, lds, P, R, S, A, calc)
+                               : batch_loop_launch<256, false, Oracle>(s, sh, lds, P, R, S, A, calc);
+        }
+        if (rc) return rc;
+        HIPCHK(hipGetLastError());
+        int nstopped = 0;
+        HIPCHK(hipMemcpyAsync(&nstopped, S.nstopped, sizeof(int), hipMemcpyDeviceToHost, s->stream));
+        HIPCHK(hipStreamSynchronize(s->stream));
+        if ((long long)nstopped >= st.B) break;
+    }
+    std::vector<int32_t> has(B);
+    std::vector<long long> niter(B);
+    HIPCHK(hipMemcpy(has.data(), S.has_best, B * sizeof(int), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(status_out, S.status, B * sizeof(int), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(niter.data(), st.d_niter, B * sizeof(long long), hipMemcpyDeviceToHost));
+    if (!feas) HIPCHK(hipMemcpy(gamma_inout, st.d_gamma, B * sizeof(double), hipMemcpyDeviceToHost));
+    for (size_t b = 0; b < B; ++b) {
+        has_out[b] = has[b];
+        niter_out[b] = niter[b];
+    }
+    if (x_out) {
+        std::vector<double> xb(B * n);
+        HIPCHK(hipMemcpy(xb.data(), st.d_xbest, B * n * sizeof(double), hipMemcpyDeviceToHost));
+        for (size_t b = 0; b < B; ++b)
+            if (has[b]) memcpy(x_out + b * n, xb.data() + b * n, n * sizeof(double));
+    }
+    return 0;
+}
+
+}  // namespace

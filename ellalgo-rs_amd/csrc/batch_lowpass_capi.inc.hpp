@@ -1,7 +1,6 @@
 // batch_lowpass_capi.inc.hpp -- C ABI of the batched device-resident low-pass filter design loop
 // (include/ellhip_batch_lowpass.h).  Included at the end of ellhip_capi.hip, after lowpass_capi.inc.hpp (it builds the
-// table with the same lp_fill_rows), batch_capi.inc.hpp (it drives the batch engine's handle directly) and
-// batch_lmi_capi.inc.hpp (batch_lmi_allow_lds).
+// table with the same lp_fill_rows) and batch_loop_capi.inc.hpp (the loop state, the launch shapes and the driver).
 //
 // Reference: src/oracles/lowpass_oracle.rs:22-151 (oracle), src/cutting_plane.rs:205-227, 286-313 (loops).
 #include "../../include/ellhip_batch_lowpass.h"
@@ -9,11 +8,10 @@
 #include "batch_lowpass_kernels.hpp"
 
 struct ellhip_batch_lowpass {
-    int device = 0;
+    BatchLoopBuffers loop;        // device, B, n, stream, the loop state (d_gamma: also assess_optim)
     long long B = 0;
     int n = 0;
     int mdim = 0;
-    int chunk = 256;
     std::vector<int> bands;       // host copy of [B][2]: nwpass, nwstop (reset, state)
     double* d_spec = nullptr;     // [15 n][n]
     double* d_specT = nullptr;    // [n][15 n]
@@ -23,22 +21,16 @@ struct ellhip_batch_lowpass {
     int* d_kmax = nullptr;        // [B]
     double* d_fmax = nullptr;     // [B]
     double* d_spsq = nullptr;     // [B]
-    double* d_gamma = nullptr;    // [B]
-    double* d_xbest = nullptr;    // [B][n]
-    long long* d_niter = nullptr; // [B]
-    int* d_ints = nullptr;        // has_best [B], stopped [B], status [B], nstopped [1]
     double* d_x = nullptr;        // assess: [B][n]
     double* d_grad = nullptr;     // assess: [B][n]
     double* d_beta = nullptr;     // assess: beta0 [B], beta1 [B]
     int* d_aints = nullptr;       // assess: has_beta1 [B], answer [B]
-    hipStream_t stream = nullptr;
 };
 
 namespace {
 
-BatchLpArrays batch_lowpass_arrays(ellhip_batch_lowpass* o) {
-    const size_t B = (size_t)o->B;
-    BatchLpArrays A;
+BatchLpOracle::Args batch_lowpass_args(const ellhip_batch_lowpass* o) {
+    BatchLpOracle::Args A;
     A.spec = o->d_spec;
     A.specT = o->d_specT;
     A.bands = o->d_bands;
@@ -47,13 +39,7 @@ BatchLpArrays batch_lowpass_arrays(ellhip_batch_lowpass* o) {
     A.kmax = o->d_kmax;
     A.fmax = o->d_fmax;
     A.spsq = o->d_spsq;
-    A.gamma = o->d_gamma;
-    A.xbest = o->d_xbest;
-    A.has_best = o->d_ints;
-    A.niter = o->d_niter;
-    A.stopped = o->d_ints + B;
-    A.status = o->d_ints + 2 * B;
-    A.nstopped = o->d_ints + 3 * B;
+    A.mdim = o->mdim;
     return A;
 }
 
@@ -80,70 +66,8 @@ int batch_lowpass_run(ellhip_batch* s, ellhip_batch_lowpass* o, int feas, double
                       bool stable = false) {
     if (!s || !o || !has_out || !niter_out || !status_out || (!feas && !gamma_inout))
         return fail(ELLHIP_E_INVALID, "NULL argument");
-    if (const int rc = batch_loop_check(s, stable, "batched lowpass loop")) return rc;
-    if (s->B != o->B || s->n != o->n)
-        return fail(ELLHIP_E_INVALID, "batched lowpass loop: spaces and oracle differ in B or n");
-    if (s->device != o->device)
-        return fail(ELLHIP_E_INVALID, "batched lowpass loop: spaces and oracle live on different devices");
-    if (max_iters < 0) return fail(ELLHIP_E_INVALID, "max_iters must be >= 0");
-    const size_t B = (size_t)o->B, n = (size_t)o->n;
-    const BatchLoopShape sh = batch_loop_shape(s, stable);
-    const size_t lds = (size_t)sh.epw * (sh.space_doubles + batch_lowpass_lds_doubles(s->n)) * sizeof(double);
-    if (lds > BATCH_LMI_LDS_MAX) return fail(ELLHIP_E_INVALID, "batched lowpass loop: this n needs more LDS than a workgroup has");
-    DeviceGuard guard(s->device);
-    BatchLpArrays A = batch_lowpass_arrays(o);
-    HIPCHK(hipStreamSynchronize(s->stream));
-    HIPCHK(hipStreamSynchronize(o->stream));
-    HIPCHK(fill_now(o->d_ints, 0, (3 * B + 1) * sizeof(int), s->stream));
-    HIPCHK(fill_now(o->d_niter, 0, B * sizeof(long long), s->stream));
-    if (!feas) HIPCHK(hipMemcpy(o->d_gamma, gamma_inout, B * sizeof(double), hipMemcpyHostToDevice));
-    const BatchParams P = batch_loop_params(s, sh);
-    const unsigned grid = (unsigned)((s->B + sh.epw - 1) / sh.epw);
-    const EllCalcDev calc = EllCalcDev::make(s->n, s->use_parallel_cut);
-    BatchLpLoop R;
-    R.feas = feas;
-    R.mdim = o->mdim;
-    R.max_iters = max_iters;
-    R.tol = tol;
-    for (long long done = 0; done < max_iters; done += o->chunk) {
-        R.iters = (int)std::min<long long>(o->chunk, max_iters - done);
-#define BATCH_LP_GO(TT, ST)                                                                                           \
-    do {                                                                                                              \
-        const int rc_ = batch_lmi_allow_lds(&k_batch_lowpass_loop<TT, ST>, s->device, sh.slot, lds);                  \
-        if (rc_) return rc_;                                                                                          \
-        hipLaunchKernelGGL((k_batch_lowpass_loop<TT, ST>), dim3(grid), dim3(TT), lds, s->stream, P, R, s->d_Q,        \
-                           s->d_xc, s->d_kappa, s->d_tsq, A, calc);                                                   \
-    } while (0)
-        if (stable) {
-            if (sh.T == 128) BATCH_LP_GO(128, true);
-            else BATCH_LP_GO(256, true);
-        } else if (sh.T == 64) BATCH_LP_GO(64, false);
-        else if (sh.T == 128) BATCH_LP_GO(128, false);
-        else BATCH_LP_GO(256, false);
-#undef BATCH_LP_GO
-        HIPCHK(hipGetLastError());
-        int nstopped = 0;
-        HIPCHK(hipMemcpyAsync(&nstopped, A.nstopped, sizeof(int), hipMemcpyDeviceToHost, s->stream));
-        HIPCHK(hipStreamSynchronize(s->stream));
-        if ((long long)nstopped >= o->B) break;
-    }
-    std::vector<int32_t> has(B);
-    std::vector<long long> niter(B);
-    HIPCHK(hipMemcpy(has.data(), A.has_best, B * sizeof(int), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(status_out, A.status, B * sizeof(int), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(niter.data(), o->d_niter, B * sizeof(long long), hipMemcpyDeviceToHost));
-    if (!feas) HIPCHK(hipMemcpy(gamma_inout, o->d_gamma, B * sizeof(double), hipMemcpyDeviceToHost));
-    for (size_t b = 0; b < B; ++b) {
-        has_out[b] = has[b];
-        niter_out[b] = niter[b];
-    }
-    if (x_out) {
-        std::vector<double> xb(B * n);
-        HIPCHK(hipMemcpy(xb.data(), o->d_xbest, B * n * sizeof(double), hipMemcpyDeviceToHost));
-        for (size_t b = 0; b < B; ++b)
-            if (has[b]) memcpy(x_out + b * n, xb.data() + b * n, n * sizeof(double));
-    }
-    return 0;
+    return batch_loop_run<BatchLpOracle>(s, o->loop, batch_lowpass_args(o), {"batched lowpass loop", "n", ""}, stable, feas,
+                                         gamma_inout, max_iters, tol, x_out, has_out, niter_out, status_out);
 }
 
 // one oracle call per problem; ans[B] = BLP_*
@@ -151,27 +75,28 @@ int batch_lowpass_assess(ellhip_batch_lowpass* o, int optim, const double* x, do
                          double* beta0, int32_t* has_beta1, double* beta1, std::vector<int>& ans) {
     if (!o || !x || !grad_out || !beta0 || !has_beta1 || !beta1 || (optim && !gamma_inout))
         return fail(ELLHIP_E_INVALID, "NULL argument");
-    DeviceGuard guard(o->device);
+    DeviceGuard guard(o->loop.device);
     const size_t B = (size_t)o->B, n = (size_t)o->n;
-    const int T = o->n <= 64 ? 256 : 128;
-    const int epw = std::min(64, T / o->n);
-    const size_t lds = (size_t)epw * (batch_lowpass_lds_doubles(o->n) + n) * sizeof(double);  // at most 64 * 29 * 8 bytes
+    const size_t per = batch_lowpass_lds_doubles(o->n) + n;
+    const BatchRowShape sh = batch_row_shape(o->n, per);
+    const int T = sh.T, epw = sh.epw;
+    const size_t lds = (size_t)epw * per * sizeof(double);  // at most 64 * 29 * 8 bytes
     const unsigned grid = (unsigned)((o->B + epw - 1) / epw);
     double* d_beta0 = o->d_beta;
     double* d_beta1 = o->d_beta + B;
     int* d_hb1 = o->d_aints;
     int* d_ans = o->d_aints + B;
-    BatchLpArrays A = batch_lowpass_arrays(o);
+    const BatchLpOracle::Args A = batch_lowpass_args(o);
     HIPCHK(hipMemcpy(o->d_x, x, B * n * sizeof(double), hipMemcpyHostToDevice));
-    if (optim) HIPCHK(hipMemcpy(o->d_gamma, gamma_inout, B * sizeof(double), hipMemcpyHostToDevice));
+    if (optim) HIPCHK(hipMemcpy(o->loop.d_gamma, gamma_inout, B * sizeof(double), hipMemcpyHostToDevice));
 #define BATCH_LP_ASSESS(TT)                                                                                            \
-    hipLaunchKernelGGL(k_batch_lowpass_assess<TT>, dim3(grid), dim3(TT), lds, o->stream, o->B, o->n, epw, o->mdim,     \
-                       optim, A, (const double*)o->d_x, o->d_grad, d_beta0, d_hb1, d_beta1, d_ans)
+    hipLaunchKernelGGL(k_batch_lowpass_assess<TT>, dim3(grid), dim3(TT), lds, o->loop.stream, o->B, o->n, epw, optim,  \
+                       A, o->loop.d_gamma, (const double*)o->d_x, o->d_grad, d_beta0, d_hb1, d_beta1, d_ans)
     if (T == 128) BATCH_LP_ASSESS(128);
     else BATCH_LP_ASSESS(256);
 #undef BATCH_LP_ASSESS
     HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(o->stream));
+    HIPCHK(hipStreamSynchronize(o->loop.stream));
     std::vector<double> g(B * n), b0(B), b1(B);
     std::vector<int> hb1(B);
     ans.resize(B);
@@ -180,7 +105,7 @@ int batch_lowpass_assess(ellhip_batch_lowpass* o, int optim, const double* x, do
     HIPCHK(hipMemcpy(b0.data(), d_beta0, B * sizeof(double), hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(b1.data(), d_beta1, B * sizeof(double), hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(hb1.data(), d_hb1, B * sizeof(int), hipMemcpyDeviceToHost));
-    if (optim) HIPCHK(hipMemcpy(gamma_inout, o->d_gamma, B * sizeof(double), hipMemcpyDeviceToHost));
+    if (optim) HIPCHK(hipMemcpy(gamma_inout, o->loop.d_gamma, B * sizeof(double), hipMemcpyDeviceToHost));
     for (size_t b = 0; b < B; ++b) {  // a problem without a cut leaves its outputs as the caller had them
         if (ans[b] != BLP_CUT && ans[b] != BLP_SHRUNK) continue;
         memcpy(grad_out + b * n, g.data() + b * n, n * sizeof(double));
@@ -225,7 +150,6 @@ int ellhip_batch_lowpass_create(ellhip_batch_lowpass** out, int64_t B, int64_t n
     if (device >= ndev) return fail(ELLHIP_E_INVALID, "device index out of range");
     ellhip_batch_lowpass* o = new (std::nothrow) ellhip_batch_lowpass();
     if (!o) return fail(ELLHIP_E_NOMEM, "host allocation failed");
-    o->device = device;
     o->B = B;
     o->n = (int)n;
     o->mdim = (int)mdim;
@@ -243,7 +167,7 @@ int ellhip_batch_lowpass_create(ellhip_batch_lowpass** out, int64_t B, int64_t n
     else lp_fill_rows(rows.data(), (long long)n, mdim, 0, mdim);
     for (size_t r = 0; r < (size_t)mdim; ++r)
         for (size_t j = 0; j < sn; ++j) cols[j * (size_t)mdim + r] = rows[r * sn + j];
-    hipError_t e = hipStreamCreateWithFlags(&o->stream, hipStreamNonBlocking);
+    hipError_t e = batch_loop_alloc(o->loop, device, B, (int)n);
     if (e == hipSuccess) e = hipMalloc(&o->d_spec, tab * sizeof(double));
     if (e == hipSuccess) e = hipMalloc(&o->d_specT, tab * sizeof(double));
     if (e == hipSuccess) e = hipMalloc(&o->d_bands, 2 * sB * sizeof(int));
@@ -252,10 +176,6 @@ int ellhip_batch_lowpass_create(ellhip_batch_lowpass** out, int64_t B, int64_t n
     if (e == hipSuccess) e = hipMalloc(&o->d_kmax, sB * sizeof(int));
     if (e == hipSuccess) e = hipMalloc(&o->d_fmax, sB * sizeof(double));
     if (e == hipSuccess) e = hipMalloc(&o->d_spsq, sB * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc(&o->d_gamma, sB * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc(&o->d_xbest, sB * sn * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc(&o->d_niter, sB * sizeof(long long));
-    if (e == hipSuccess) e = hipMalloc(&o->d_ints, (3 * sB + 1) * sizeof(int));
     if (e == hipSuccess) e = hipMalloc(&o->d_x, sB * sn * sizeof(double));
     if (e == hipSuccess) e = hipMalloc(&o->d_grad, sB * sn * sizeof(double));
     if (e == hipSuccess) e = hipMalloc(&o->d_beta, 2 * sB * sizeof(double));
@@ -267,10 +187,8 @@ int ellhip_batch_lowpass_create(ellhip_batch_lowpass** out, int64_t B, int64_t n
     if (e == hipSuccess) e = hipMemcpy(o->d_bands, bands.data(), 2 * sB * sizeof(int), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(o->d_lims, lims.data(), 2 * sB * sizeof(double), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(o->d_spsq, sp_sq, sB * sizeof(double), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(o->d_gamma, sp_sq, sB * sizeof(double), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = fill_now(o->d_xbest, 0, sB * sn * sizeof(double), o->stream);
-    if (e == hipSuccess) e = fill_now(o->d_grad, 0, sB * sn * sizeof(double), o->stream);
-    if (e == hipSuccess) e = fill_now(o->d_ints, 0, (3 * sB + 1) * sizeof(int), o->stream);
+    if (e == hipSuccess) e = hipMemcpy(o->loop.d_gamma, sp_sq, sB * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = fill_now(o->d_grad, 0, sB * sn * sizeof(double), o->loop.stream);
     if (e != hipSuccess) return bail(fail(ELLHIP_E_HIP, "batched lowpass upload", e));
     const int rc = batch_lowpass_fresh(o);
     if (rc) return bail(rc);
@@ -280,13 +198,12 @@ int ellhip_batch_lowpass_create(ellhip_batch_lowpass** out, int64_t B, int64_t n
 
 void ellhip_batch_lowpass_destroy(ellhip_batch_lowpass* o) {
     if (!o) return;
-    DeviceGuard guard(o->device);
-    if (o->stream) (void)hipStreamSynchronize(o->stream);
-    void* bufs[] = {o->d_spec,  o->d_specT, o->d_bands, o->d_lims, o->d_cursor, o->d_kmax, o->d_fmax, o->d_spsq,
-                    o->d_gamma, o->d_xbest, o->d_niter, o->d_ints, o->d_x,      o->d_grad, o->d_beta, o->d_aints};
+    DeviceGuard guard(o->loop.device);
+    batch_loop_free(o->loop);
+    void* bufs[] = {o->d_spec, o->d_specT, o->d_bands, o->d_lims,  o->d_cursor, o->d_kmax,
+                    o->d_fmax, o->d_spsq,  o->d_x,     o->d_grad,  o->d_beta,   o->d_aints};
     for (void* p : bufs)
         if (p) (void)hipFree(p);
-    if (o->stream) (void)hipStreamDestroy(o->stream);
     delete o;
 }
 
@@ -316,8 +233,8 @@ int ellhip_batch_lowpass_assess_optim(ellhip_batch_lowpass* o, const double* x, 
 
 int ellhip_batch_lowpass_state(ellhip_batch_lowpass* o, int32_t* ints7, double* doubles2) {
     if (!o) return fail(ELLHIP_E_INVALID, "NULL handle");
-    DeviceGuard guard(o->device);
-    HIPCHK(hipStreamSynchronize(o->stream));
+    DeviceGuard guard(o->loop.device);
+    HIPCHK(hipStreamSynchronize(o->loop.stream));
     const size_t B = (size_t)o->B;
     if (ints7) {
         std::vector<int> cur(4 * B), kmax(B);
@@ -348,14 +265,14 @@ int ellhip_batch_lowpass_state(ellhip_batch_lowpass* o, int32_t* ints7, double* 
 
 int ellhip_batch_lowpass_reset(ellhip_batch_lowpass* o) {
     if (!o) return fail(ELLHIP_E_INVALID, "NULL handle");
-    DeviceGuard guard(o->device);
-    HIPCHK(hipStreamSynchronize(o->stream));
+    DeviceGuard guard(o->loop.device);
+    HIPCHK(hipStreamSynchronize(o->loop.stream));
     return batch_lowpass_fresh(o);
 }
 
 int ellhip_batch_lowpass_get_spectrum(ellhip_batch_lowpass* o, double* out) {
     if (!o || !out) return fail(ELLHIP_E_INVALID, "NULL argument");
-    DeviceGuard guard(o->device);
+    DeviceGuard guard(o->loop.device);
     HIPCHK(hipMemcpy(out, o->d_spec, (size_t)o->mdim * (size_t)o->n * sizeof(double), hipMemcpyDeviceToHost));
     return 0;
 }
@@ -372,10 +289,7 @@ int ellhip_batch_lowpass_feas(ellhip_batch* spaces, ellhip_batch_lowpass* o, int
 }
 
 int ellhip_batch_lowpass_set_chunk(ellhip_batch_lowpass* o, int64_t iters) {
-    if (!o) return fail(ELLHIP_E_INVALID, "NULL handle");
-    if (iters < 1 || iters > 4096) return fail(ELLHIP_E_INVALID, "batched lowpass: chunk must be in 1..4096");
-    o->chunk = (int)iters;
-    return 0;
+    return batch_loop_set_chunk(o ? &o->loop : nullptr, iters, "batched lowpass");
 }
 
 }  // extern "C"

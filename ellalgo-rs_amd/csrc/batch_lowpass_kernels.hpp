@@ -1,8 +1,7 @@
-// batch_lowpass_kernels.hpp -- B independent FIR low-pass design problems of one filter length, oracle and ellipsoid
-// update in one kernel (include/ellhip_batch_lowpass.h).
+// batch_lowpass_kernels.hpp -- the oracle of B independent FIR low-pass design problems of one filter length, as a policy
+// of the loop kernel (include/ellhip_batch_lowpass.h; the loop itself: batch_loop_kernels.hpp).
 //
-// A workgroup owns the ellipsoids the batch engine gives it (batch_kernels.hpp: thread (e, i) = row i of local
-// ellipsoid e, Q in LDS) and, for each of them, runs up to `iters` rounds of
+// For every ellipsoid of its workgroup k_batch_loop<T, STABLE, BatchLpOracle> runs rounds of
 //     oracle (LowpassOracle::assess_feas / assess_optim, src/oracles/lowpass_oracle.rs:58-150)
 //  -> scalar stage + rank-1 (batch_cut_apply, the same code k_batch_update runs)
 // without leaving the kernel.  Every `row . x` is the reference's left fold from 0.0 with a separately rounded multiply
@@ -24,37 +23,34 @@
 // n threads read one row) and transposed [j][row] for the folds (the n threads read n consecutive rows).
 //
 // Barriers are workgroup-wide and the instances of a workgroup sit in different bands, so the walk is driven by
-// __syncthreads_or votes; every loop is bounded by iters, 15 + 4 steps and n; no thread waits on another workgroup.
+// __syncthreads_or votes; every loop is bounded by 15 + 4 steps and n; no thread waits on another workgroup.
 #pragma once
 
 #include <climits>
 
-#include "batch_stable_apply.hpp"
+#include "batch_loop_kernels.hpp"
 
 namespace ellhip {
 
-// oracle and loop scalars (LDS, per instance)
+// oracle scalars (LDS, per instance), after the loop's own (batch_loop_kernels.hpp)
 enum : int {
-    BO_B0 = 0,       // the cut's beta0
-    BO_B1 = 1,       // beta1
-    BO_HB1 = 2,      // 1: the cut is ParallelCut(beta0, Some(beta1))
-    BO_RES = 3,      // the walk's answer (BLP_*), written where the walk ends
-    BO_ROW = 4,      // the row the gradient is taken from; -1: the x[0] < 0 station (g = -e0)
-    BO_NEG = 5,      // 1: g = -row
-    BO_FMAX = 6,
-    BO_KMAX = 7,
-    BO_SPSQ = 8,     // the oracle's sp_sq field
-    BO_GAMMA = 9,    // the loop's gamma
-    BO_NITER = 10,
-    BO_STOPPED = 11,
-    BO_HASBEST = 12,
-    BO_STATUS = 13,
+    BO_GAMMA = BL_GAMMA,  // the loop's gamma
+    BO_B0 = 5,       // the cut's beta0
+    BO_B1 = 6,       // beta1
+    BO_HB1 = 7,      // 1: the cut is ParallelCut(beta0, Some(beta1))
+    BO_RES = 8,      // the walk's answer (BLP_*), written where the walk ends
+    BO_ROW = 9,      // the row the gradient is taken from; -1: the x[0] < 0 station (g = -e0)
+    BO_NEG = 10,     // 1: g = -row
+    BO_FMAX = 11,
+    BO_KMAX = 12,
+    BO_SPSQ = 13,    // the oracle's sp_sq field
     BO_KEY = 14,     // unsigned long long: largest key of the stopband values
     BO_FIRST = 15,   // int: first violating position
     BO_KPOS = 16,    // int: first position that holds the largest value
     BO_ANS = 17,     // the call's answer (BLP_*), after the assess_optim tail
     BATCH_LP_SCALARS = 20,
 };
+static_assert(BO_B0 == BL_SCALARS, "the oracle's scalars follow the loop's");
 enum : int { BLP_WALK = -1, BLP_FEAS = 0, BLP_CUT = 1, BLP_SHRUNK = 2, BLP_ERR = 3 };
 
 // doubles of LDS the oracle needs per instance: x and the scalars
@@ -259,171 +255,81 @@ __device__ __forceinline__ void batch_lowpass_oracle(const int mdim, const bool 
     __syncthreads();
 }
 
-struct BatchLpArrays {
-    const double* spec;    // [15 n][n]
-    const double* specT;   // [n][15 n]
-    const int* bands;      // [B][2]: nwpass, nwstop
-    const double* lims;    // [B][2]: lp_sq, up_sq
-    int* cursor;           // [B][4]: idx1, idx2, idx3, more_alt
-    int* kmax;             // [B]
-    double* fmax;          // [B]
-    double* spsq;          // [B]
-    double* gamma;         // [B]
-    double* xbest;         // [B][n]
-    int* has_best;         // [B]
-    long long* niter;      // [B]
-    int* stopped;          // [B]
-    int* status;           // [B]
-    int* nstopped;         // [1]
-};
-
-struct BatchLpLoop {
-    int iters;            // iterations this launch may run
-    int feas;             // 1: cutting_plane_feas
-    int mdim;             // 15 n
-    long long max_iters;
-    double tol;
-};
-
-// cutting_plane_optim (src/cutting_plane.rs:286-313) / cutting_plane_feas (:205-227) for every instance of the workgroup.
-// Loop state per instance lives in HBM between launches (BatchLpArrays).
-// STABLE: the spaces are EllStable buffers and a cut is batch_stable_cut_apply (batch_stable_apply.hpp).
-template <int T, bool STABLE = false>
-__global__ __launch_bounds__(T) void k_batch_lowpass_loop(BatchParams P, BatchLpLoop R, double* __restrict__ Q,
-                                                          double* __restrict__ xc, double* __restrict__ kappa,
-                                                          double* __restrict__ tsq, BatchLpArrays A, EllCalcDev calc) {
-    extern __shared__ double sm[];
-    const int n = P.n, pitch = P.pitch;
-    const int tid = threadIdx.x;
-    const int e = tid / n, i = tid - e * n;
-    const long long b = (long long)blockIdx.x * P.epw + e;
-    const bool active = e < P.epw && b < P.B;
-    if (!__syncthreads_or(active && A.stopped[b] == 0)) return;  // all of this workgroup's instances have stopped
-
-    const size_t per = batch_space_lds_doubles<STABLE>(n);
-    const size_t lper = batch_lowpass_lds_doubles(n);
-    const int el = e < P.epw ? e : 0;
-    double* q = sm + (size_t)el * per;
-    double* g = q + (size_t)n * pitch;
-    double* sc = q + batch_space_scalars_at<STABLE>(n);  // as in k_batch_update
-    double* lx = sm + (size_t)P.epw * per + (size_t)el * lper;
-    double* osc = lx + n;
-
-    const long long b_first = (long long)blockIdx.x * P.epw;
-    const int nb = (int)((P.B - b_first < P.epw) ? P.B - b_first : P.epw);
-    double* Qwg = Q + b_first * (long long)n * n;
-    batch_copy<T, true>(sm, Qwg, nb * n * n, n, pitch, (int)per, tid);
-    double xci = 0.0, xb = 0.0;
-    BatchLpBands K{1, 1, 0.0, 0.0};
-    BatchLpCursor c{-1, 0, 0, 1};
-    if (active) {
-        xci = xc[b * n + i];
-        xb = A.xbest[b * n + i];
-        K.nwpass = A.bands[2 * b];
-        K.nwstop = A.bands[2 * b + 1];
-        K.lp_sq = A.lims[2 * b];
-        K.up_sq = A.lims[2 * b + 1];
-        c.idx1 = A.cursor[4 * b];
-        c.idx2 = A.cursor[4 * b + 1];
-        c.idx3 = A.cursor[4 * b + 2];
-        c.more_alt = A.cursor[4 * b + 3];
+// The oracle as the loop kernel's policy (batch_loop_kernels.hpp).  Per instance in HBM: the bands and limits (constant),
+// the cursor, fmax / kmax and sp_sq.
+struct BatchLpOracle {
+    struct Args {
+        const double* spec;   // [15 n][n]
+        const double* specT;  // [n][15 n]
+        const int* bands;     // [B][2]: nwpass, nwstop
+        const double* lims;   // [B][2]: lp_sq, up_sq
+        int* cursor;          // [B][4]: idx1, idx2, idx3, more_alt
+        int* kmax;            // [B]
+        double* fmax;         // [B]
+        double* spsq;         // [B]
+        int mdim;             // 15 n
+    };
+    struct Regs {
+        BatchLpBands K{1, 1, 0.0, 0.0};
+        BatchLpCursor c{-1, 0, 0, 1};
+    };
+    static __host__ __device__ inline size_t lds_doubles(const Args&, int n) { return batch_lowpass_lds_doubles(n); }
+    static __device__ __forceinline__ size_t scalars_at(const Args&, int n) { return (size_t)n; }
+    static __device__ __forceinline__ void load(const Args& A, bool active, long long b, int i, int n, double* blk, Regs& r) {
+        if (active) {
+            r.K.nwpass = A.bands[2 * b];
+            r.K.nwstop = A.bands[2 * b + 1];
+            r.K.lp_sq = A.lims[2 * b];
+            r.K.up_sq = A.lims[2 * b + 1];
+            r.c.idx1 = A.cursor[4 * b];
+            r.c.idx2 = A.cursor[4 * b + 1];
+            r.c.idx3 = A.cursor[4 * b + 2];
+            r.c.more_alt = A.cursor[4 * b + 3];
+        }
+        if (active && i == 0) {
+            double* osc = blk + n;
+            osc[BO_FMAX] = A.fmax[b];
+            osc[BO_KMAX] = (double)A.kmax[b];
+            osc[BO_SPSQ] = A.spsq[b];
+        }
     }
-    if (active && i == 0) {
-        sc[3] = (double)ST_SUCCESS;
-        sc[4] = kappa[b];
-        sc[5] = tsq[b];
-        osc[BO_FMAX] = A.fmax[b];
-        osc[BO_KMAX] = (double)A.kmax[b];
-        osc[BO_SPSQ] = A.spsq[b];
-        osc[BO_GAMMA] = A.gamma[b];
-        osc[BO_NITER] = (double)A.niter[b];
-        osc[BO_STOPPED] = (double)A.stopped[b];
-        osc[BO_HASBEST] = (double)A.has_best[b];
-        osc[BO_STATUS] = (double)A.status[b];
-    }
-    __syncthreads();
-
-    const bool lane_ok = tid < P.epw && b_first + tid < P.B;
-    const int es = tid < P.epw ? tid : 0;
-    double* q_s = sm + (size_t)es * per;
-    const double* osc_s = sm + (size_t)P.epw * per + (size_t)es * lper + n;
-    const bool optim = R.feas == 0;
-
-    for (int it = 0; it < R.iters; ++it) {
-        const bool live = active && osc[BO_STOPPED] == 0.0;
-        if (!__syncthreads_or(live)) break;
+    static __device__ __forceinline__ void assess(const Args& A, const BatchLoopRun& R, bool live, int i, int n, double xci,
+                                                  double* blk, Regs& r, double* g) {
+        double* osc = blk + n;
+        const bool optim = R.feas == 0;
         if (live) {
-            lx[i] = xci;
+            blk[i] = xci;
             if (optim && i == 0) osc[BO_SPSQ] = osc[BO_GAMMA];  //          self.sp_sq = *sp_sq, lowpass_oracle.rs:140
         }
         __syncthreads();
-        batch_lowpass_oracle(R.mdim, live, i, n, optim, A.spec, A.specT, K, c, lx, osc, g);
-        const int ans = live ? (int)osc[BO_ANS] : BLP_ERR;
-        const bool shrunk = ans == BLP_SHRUNK;
-        const bool found = R.feas && ans == BLP_FEAS;  // cutting_plane_feas: a feasible point ends the loop  :217-220
-        if (shrunk || found) xb = xci;                 // x_best = Some(space.xc())                           :303
-        const bool upd = live && (ans == BLP_CUT || shrunk);
-        const int ans_s = lane_ok ? (int)osc_s[BO_ANS] : BLP_ERR;
-        const bool lane = lane_ok && osc_s[BO_STOPPED] == 0.0 && (ans_s == BLP_CUT || ans_s == BLP_SHRUNK);
-        const int kind = (lane && ans_s == BLP_SHRUNK) ? CUT_CENTRAL : CUT_BIAS;  //                          :301-307
-        const double b0 = lane ? osc_s[BO_B0] : 0.0;
-        const double b1 = lane ? osc_s[BO_B1] : 0.0;
-        const int hb1 = lane ? (int)osc_s[BO_HB1] : 0;
-        batch_space_cut_apply<STABLE>(P, calc, upd, i, q, xci, lane, q_s, kind, b0, hb1, b1, [](int, double) {});
-        if (live && i == 0) {
-            if (shrunk || found) osc[BO_HASBEST] = 1.0;
-            bool stop;
-            if (found) {
-                osc[BO_STATUS] = (double)ST_SUCCESS;
-                stop = true;
-            } else if (!upd) {  // feasible, but no stopband row to take the objective from
-                osc[BO_STATUS] = (double)ST_UNKNOWN;
-                stop = true;
-            } else if (sc[3] != (double)ST_SUCCESS || sc[5] < R.tol) {  //                                    :308 / :222
-                osc[BO_STATUS] = sc[3];
-                stop = true;
-            } else {
-                const double done = osc[BO_NITER] + 1.0;
-                osc[BO_NITER] = done;
-                osc[BO_STATUS] = (double)ST_SUCCESS;
-                stop = done >= (double)R.max_iters;
-            }
-            if (stop) {
-                osc[BO_STOPPED] = 1.0;
-                atomicAdd(A.nstopped, 1);
-            }
-        }
-        __syncthreads();
+        batch_lowpass_oracle(A.mdim, live, i, n, optim, A.spec, A.specT, r.K, r.c, blk, osc, g);
     }
-
-    if (active) {
-        xc[b * n + i] = xci;
-        if (osc[BO_HASBEST] != 0.0) A.xbest[b * n + i] = xb;
+    // BLP_FEAS under cutting_plane_optim never leaves the oracle (it shrinks, or has no stopband row to take the
+    // objective from: BLP_ERR)
+    static __device__ __forceinline__ BatchOutcome outcome(const Args&, int feas, const double* osc) {
+        const int ans = (int)osc[BO_ANS];
+        const int what = ans == BLP_CUT ? BOUT_CUT
+                         : ans == BLP_SHRUNK ? BOUT_SHRUNK
+                         : (feas && ans == BLP_FEAS) ? BOUT_FEAS
+                                                     : BOUT_NONE;
+        return BatchOutcome{what, osc[BO_B0], (int)osc[BO_HB1], osc[BO_B1]};
     }
-    if (active && i == 0) {
-        kappa[b] = sc[4];
-        tsq[b] = sc[5];
-        A.cursor[4 * b] = c.idx1;
-        A.cursor[4 * b + 1] = c.idx2;
-        A.cursor[4 * b + 2] = c.idx3;
-        A.cursor[4 * b + 3] = c.more_alt;
+    static __device__ __forceinline__ void store(const Args& A, long long b, const double* osc, const Regs& r) {
+        A.cursor[4 * b] = r.c.idx1;
+        A.cursor[4 * b + 1] = r.c.idx2;
+        A.cursor[4 * b + 2] = r.c.idx3;
+        A.cursor[4 * b + 3] = r.c.more_alt;
         A.fmax[b] = osc[BO_FMAX];
         A.kmax[b] = (int)osc[BO_KMAX];
         A.spsq[b] = osc[BO_SPSQ];
-        A.gamma[b] = osc[BO_GAMMA];
-        A.niter[b] = (long long)osc[BO_NITER];
-        A.stopped[b] = (int)osc[BO_STOPPED];
-        A.has_best[b] = (int)osc[BO_HASBEST];
-        A.status[b] = (int)osc[BO_STATUS];
     }
-    batch_copy<T, false>(sm, Qwg, nb * n * n, n, pitch, (int)per, tid);
-}
+};
 
 // One oracle call per instance at x[B][n]: the same device function, without an ellipsoid.  optim: assess_optim with
-// A.gamma in and out; ans_out[B] = BLP_*; grad_out rows and the cut values are written for BLP_CUT and BLP_SHRUNK only.
+// gamma in and out; ans_out[B] = BLP_*; grad_out rows and the cut values are written for BLP_CUT and BLP_SHRUNK only.
 template <int T>
-__global__ __launch_bounds__(T) void k_batch_lowpass_assess(long long B, int n, int epw, int mdim, int optim,
-                                                            BatchLpArrays A, const double* __restrict__ x,
+__global__ __launch_bounds__(T) void k_batch_lowpass_assess(long long B, int n, int epw, int optim, BatchLpOracle::Args A,
+                                                            double* __restrict__ gamma_io, const double* __restrict__ x,
                                                             double* __restrict__ grad_out, double* __restrict__ beta0,
                                                             int* __restrict__ has_beta1, double* __restrict__ beta1,
                                                             int* __restrict__ ans_out) {
@@ -436,38 +342,20 @@ __global__ __launch_bounds__(T) void k_batch_lowpass_assess(long long B, int n, 
     double* lx = sm + (size_t)(e < epw ? e : 0) * lper;
     double* osc = lx + n;
     double* g = osc + BATCH_LP_SCALARS;
-    BatchLpBands K{1, 1, 0.0, 0.0};
-    BatchLpCursor c{-1, 0, 0, 1};
-    if (active) {
-        lx[i] = x[b * n + i];
-        K.nwpass = A.bands[2 * b];
-        K.nwstop = A.bands[2 * b + 1];
-        K.lp_sq = A.lims[2 * b];
-        K.up_sq = A.lims[2 * b + 1];
-        c.idx1 = A.cursor[4 * b];
-        c.idx2 = A.cursor[4 * b + 1];
-        c.idx3 = A.cursor[4 * b + 2];
-        c.more_alt = A.cursor[4 * b + 3];
-    }
+    BatchLpOracle::Regs r;
+    BatchLpOracle::load(A, active, b, i, n, lx, r);
+    if (active) lx[i] = x[b * n + i];
     if (active && i == 0) {
-        osc[BO_FMAX] = A.fmax[b];
-        osc[BO_KMAX] = (double)A.kmax[b];
-        osc[BO_GAMMA] = A.gamma[b];
-        osc[BO_SPSQ] = optim ? A.gamma[b] : A.spsq[b];  //                  self.sp_sq = *sp_sq, lowpass_oracle.rs:140
+        osc[BO_GAMMA] = gamma_io[b];
+        if (optim) osc[BO_SPSQ] = gamma_io[b];  //                          self.sp_sq = *sp_sq, lowpass_oracle.rs:140
     }
     __syncthreads();
-    batch_lowpass_oracle(mdim, active, i, n, optim != 0, A.spec, A.specT, K, c, lx, osc, g);
+    batch_lowpass_oracle(A.mdim, active, i, n, optim != 0, A.spec, A.specT, r.K, r.c, lx, osc, g);
     const int ans = active ? (int)osc[BO_ANS] : BLP_ERR;
     if (active && (ans == BLP_CUT || ans == BLP_SHRUNK)) grad_out[b * n + i] = g[i];
     if (active && i == 0) {
-        A.cursor[4 * b] = c.idx1;
-        A.cursor[4 * b + 1] = c.idx2;
-        A.cursor[4 * b + 2] = c.idx3;
-        A.cursor[4 * b + 3] = c.more_alt;
-        A.fmax[b] = osc[BO_FMAX];
-        A.kmax[b] = (int)osc[BO_KMAX];
-        A.spsq[b] = osc[BO_SPSQ];
-        A.gamma[b] = osc[BO_GAMMA];
+        BatchLpOracle::store(A, b, osc, r);
+        gamma_io[b] = osc[BO_GAMMA];
         ans_out[b] = ans;
         if (ans == BLP_CUT || ans == BLP_SHRUNK) {
             beta0[b] = osc[BO_B0];

@@ -1,8 +1,8 @@
 // batch_stable_loops_capi.inc.hpp -- C ABI of the batched device-resident cutting-plane loops on EllStable batch handles
 // (include/ellhip_batch_stable_loops.h).  Included at the end of ellhip_capi.hip, after batch_lmi_capi.inc.hpp,
 // batch_lowpass_capi.inc.hpp and batch_svm_capi.inc.hpp: it runs their launch helpers (batch_lmi_run, batch_lowpass_run,
-// batch_svm_run) with the EllStable instantiation of each loop kernel (batch_stable_apply.hpp), so the checks, the chunked
-// relaunch and the copies out are the Ell entry points' own.
+// batch_svm_run) with the EllStable instantiation of k_batch_loop (batch_loop_kernels.hpp, batch_stable_apply.hpp), so the
+// checks, the chunked relaunch and the copies out are the Ell entry points' own (batch_loop_run).
 //
 // Reference: src/ell_stable.rs:52-125 (update_core), :139-153 (update_bias_cut / update_central_cut),
 // src/cutting_plane.rs:205-227, 286-313 (loops), tests/lmi_tests.rs:201-225 (the LMI problems on EllStable).

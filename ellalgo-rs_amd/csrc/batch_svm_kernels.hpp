@@ -1,8 +1,7 @@
-// batch_svm_kernels.hpp -- B independent SvmOracle problems of one shape (m samples, nfeat features), oracle and ellipsoid
-// update in one kernel (include/ellhip_batch_svm.h).
+// batch_svm_kernels.hpp -- the oracle of B independent SvmOracle problems of one shape (m samples, nfeat features), as a
+// policy of the loop kernel (include/ellhip_batch_svm.h; the loop itself: batch_loop_kernels.hpp).
 //
-// A workgroup owns the ellipsoids the batch engine gives it (batch_kernels.hpp: thread (e, i) = row i of local ellipsoid
-// e, Q in LDS) and, for each of them, runs up to `iters` rounds of
+// For every ellipsoid of its workgroup k_batch_loop<T, STABLE, BatchSvmOracle> runs rounds of
 //     oracle (SvmOracle::assess_optim, src/oracles/svm_oracle.rs:27-57)
 //  -> x_best = xc (src/cutting_plane.rs:303; `shrunk` is always true)
 //  -> scalar stage + rank-1 (batch_cut_apply with a central cut, the same code k_batch_update runs)
@@ -24,30 +23,27 @@
 // problems, t = b otherwise: at fold step j the n threads of an instance read n consecutive doubles.  The gradient's
 // nfeat strided reads of row idx come from the same table.  Labels are [B][m] int32.  Index arithmetic is 64-bit.
 //
-// Barriers are workgroup-wide; stopped instances are masked off and the loop is driven by __syncthreads_or votes.  Every
-// loop is bounded by iters, ceil(m / n), nfeat and n; no thread waits on another workgroup.
+// Barriers are workgroup-wide; instances that take no part are masked off.  Every loop is bounded by ceil(m / n), nfeat
+// and n; no thread waits on another workgroup.
 #pragma once
 
 #include <climits>
 
-#include "batch_stable_apply.hpp"
+#include "batch_loop_kernels.hpp"
 
 namespace ellhip {
 
-// oracle and loop scalars (LDS, per instance)
+// oracle scalars (LDS, per instance), after the loop's own (batch_loop_kernels.hpp)
 enum : int {
-    SV_B0 = 0,        // the cut's beta
-    SV_GAMMA = 1,     // the loop's gamma
-    SV_MINIDX = 2,    // the last scan's min_idx
-    SV_MINVAL = 3,    // the last scan's min_val
-    SV_NITER = 4,
-    SV_STOPPED = 5,
-    SV_HASBEST = 6,
-    SV_STATUS = 7,
+    SV_GAMMA = BL_GAMMA,  // the loop's gamma
+    SV_B0 = 5,        // the cut's beta
+    SV_MINIDX = 6,    // the last scan's min_idx
+    SV_MINVAL = 7,    // the last scan's min_val
     SV_KEY = 8,       // unsigned long long: smallest key of the threads' minima
     SV_WIDX = 9,      // int: smallest sample index among the threads that hold the winning value
     BATCH_SVM_SCALARS = 10,
 };
+static_assert(SV_B0 == BL_SCALARS, "the oracle's scalars follow the loop's");
 
 // doubles of LDS the oracle needs per instance: x and the scalars
 __host__ __device__ inline size_t batch_svm_lds_doubles(int n) { return ((size_t)n + BATCH_SVM_SCALARS) | 1; }
@@ -137,141 +133,57 @@ __device__ __forceinline__ void batch_svm_oracle(const bool live, const int i, c
     __syncthreads();
 }
 
-struct BatchSvmArrays {
-    const double* XT;      // [ntab][nfeat][ld]
-    const int* labels;     // [B][m]
-    long long tab_stride;  // nfeat * ld for per-problem tables, 0 for a shared one
-    long long* min_idx;    // [B]
-    double* min_val;       // [B]
-    double* gamma;         // [B]
-    double* xbest;         // [B][n]
-    int* has_best;         // [B]
-    long long* niter;      // [B]
-    int* stopped;          // [B]
-    int* status;           // [B]
-    int* nstopped;         // [1]
-};
-
-struct BatchSvmLoop {
-    int iters;  // iterations this launch may run
-    int m;
-    long long ld;
-    long long max_iters;
-    double tol;
-};
-
-// cutting_plane_optim (src/cutting_plane.rs:286-313) for every instance of the workgroup.  Loop state per instance lives in
-// HBM between launches (BatchSvmArrays).  STABLE: the spaces are EllStable buffers and a cut is batch_stable_cut_apply
-// (batch_stable_apply.hpp).
-template <int T, bool STABLE = false>
-__global__ __launch_bounds__(T) void k_batch_svm_loop(BatchParams P, BatchSvmLoop R, double* __restrict__ Q,
-                                                      double* __restrict__ xc, double* __restrict__ kappa,
-                                                      double* __restrict__ tsq, BatchSvmArrays A, EllCalcDev calc) {
-    extern __shared__ double sm[];
-    const int n = P.n, pitch = P.pitch;
-    const int tid = threadIdx.x;
-    const int e = tid / n, i = tid - e * n;
-    const long long b = (long long)blockIdx.x * P.epw + e;
-    const bool active = e < P.epw && b < P.B;
-    if (!__syncthreads_or(active && A.stopped[b] == 0)) return;  // all of this workgroup's instances have stopped
-
-    const size_t per = batch_space_lds_doubles<STABLE>(n);
-    const size_t lper = batch_svm_lds_doubles(n);
-    const int el = e < P.epw ? e : 0;
-    double* q = sm + (size_t)el * per;
-    double* g = q + (size_t)n * pitch;
-    double* sc = q + batch_space_scalars_at<STABLE>(n);  // as in k_batch_update
-    double* lx = sm + (size_t)P.epw * per + (size_t)el * lper;
-    double* osc = lx + n;
-
-    const long long b_first = (long long)blockIdx.x * P.epw;
-    const int nb = (int)((P.B - b_first < P.epw) ? P.B - b_first : P.epw);
-    double* Qwg = Q + b_first * (long long)n * n;
-    batch_copy<T, true>(sm, Qwg, nb * n * n, n, pitch, (int)per, tid);
-    double xci = 0.0, xb = 0.0;
-    const double* xt = A.XT;
-    const int* lab = A.labels;
-    if (active) {
-        xci = xc[b * n + i];
-        xb = A.xbest[b * n + i];
-        xt = A.XT + b * A.tab_stride;
-        lab = A.labels + b * (long long)R.m;
-    }
-    if (active && i == 0) {
-        sc[3] = (double)ST_SUCCESS;
-        sc[4] = kappa[b];
-        sc[5] = tsq[b];
-        osc[SV_B0] = 0.0;
-        osc[SV_GAMMA] = A.gamma[b];
-        osc[SV_MINIDX] = (double)A.min_idx[b];
-        osc[SV_MINVAL] = A.min_val[b];
-        osc[SV_NITER] = (double)A.niter[b];
-        osc[SV_STOPPED] = (double)A.stopped[b];
-        osc[SV_HASBEST] = (double)A.has_best[b];
-        osc[SV_STATUS] = (double)A.status[b];
-    }
-    __syncthreads();
-
-    const bool lane_ok = tid < P.epw && b_first + tid < P.B;
-    const int es = tid < P.epw ? tid : 0;
-    double* q_s = sm + (size_t)es * per;
-    const double* osc_s = sm + (size_t)P.epw * per + (size_t)es * lper + n;
-
-    for (int it = 0; it < R.iters; ++it) {
-        const bool live = active && osc[SV_STOPPED] == 0.0;
-        if (!__syncthreads_or(live)) break;
-        if (live) lx[i] = xci;
-        batch_svm_oracle(live, i, n, R.m, R.ld, xt, lab, lx, osc, g, nullptr);
-        if (live) xb = xci;  // x_best = Some(space.xc())                    src/cutting_plane.rs:303
-        const bool lane = lane_ok && osc_s[SV_STOPPED] == 0.0;
-        const double b0 = lane ? osc_s[SV_B0] : 0.0;
-        batch_space_cut_apply<STABLE>(P, calc, live, i, q, xci, lane, q_s, CUT_CENTRAL, b0, 0, 0.0,
-                                      [](int, double) {});  //                :304
-        if (live && i == 0) {
-            osc[SV_HASBEST] = 1.0;
-            bool stop;
-            if (sc[3] != (double)ST_SUCCESS || sc[5] < R.tol) {  //          :308
-                osc[SV_STATUS] = sc[3];
-                stop = true;
-            } else {
-                const double done = osc[SV_NITER] + 1.0;
-                osc[SV_NITER] = done;
-                osc[SV_STATUS] = (double)ST_SUCCESS;
-                stop = done >= (double)R.max_iters;
-            }
-            if (stop) {
-                osc[SV_STOPPED] = 1.0;
-                atomicAdd(A.nstopped, 1);
-            }
+// The oracle as the loop kernel's policy (batch_loop_kernels.hpp).  Per instance in HBM: the table, the labels and what
+// the last scan found.
+struct BatchSvmOracle {
+    struct Args {
+        const double* XT;      // [ntab][nfeat][ld]
+        const int* labels;     // [B][m]
+        long long tab_stride;  // nfeat * ld for per-problem tables, 0 for a shared one
+        long long* min_idx;    // [B]
+        double* min_val;       // [B]
+        int m;
+        long long ld;
+    };
+    struct Regs {
+        const double* xt;  // this instance's table and labels
+        const int* lab;
+    };
+    static __host__ __device__ inline size_t lds_doubles(const Args&, int n) { return batch_svm_lds_doubles(n); }
+    static __device__ __forceinline__ size_t scalars_at(const Args&, int n) { return (size_t)n; }
+    static __device__ __forceinline__ void load(const Args& A, bool active, long long b, int i, int n, double* blk, Regs& r) {
+        r.xt = A.XT + (active ? b : 0) * A.tab_stride;
+        r.lab = A.labels + (active ? b : 0) * (long long)A.m;
+        if (active && i == 0) {
+            double* osc = blk + n;
+            osc[SV_B0] = 0.0;
+            osc[SV_MINIDX] = (double)A.min_idx[b];
+            osc[SV_MINVAL] = A.min_val[b];
         }
-        __syncthreads();
     }
-
-    if (active) {
-        xc[b * n + i] = xci;
-        if (osc[SV_HASBEST] != 0.0) A.xbest[b * n + i] = xb;
+    // (no barrier after the store of x: the oracle synchronises before it reads it)
+    static __device__ __forceinline__ void assess(const Args& A, const BatchLoopRun&, bool live, int i, int n, double xci,
+                                                  double* blk, Regs& r, double* g) {
+        if (live) blk[i] = xci;
+        batch_svm_oracle(live, i, n, A.m, A.ld, r.xt, r.lab, blk, blk + n, g, nullptr);
     }
-    if (active && i == 0) {
-        kappa[b] = sc[4];
-        tsq[b] = sc[5];
-        A.gamma[b] = osc[SV_GAMMA];
+    // `shrunk` is always true (src/oracles/svm_oracle.rs:44, :56)
+    static __device__ __forceinline__ BatchOutcome outcome(const Args&, int, const double* osc) {
+        return BatchOutcome{BOUT_SHRUNK, osc[SV_B0], 0, 0.0};
+    }
+    static __device__ __forceinline__ void store(const Args& A, long long b, const double* osc, const Regs&) {
         A.min_idx[b] = (long long)osc[SV_MINIDX];
         A.min_val[b] = osc[SV_MINVAL];
-        A.niter[b] = (long long)osc[SV_NITER];
-        A.stopped[b] = (int)osc[SV_STOPPED];
-        A.has_best[b] = (int)osc[SV_HASBEST];
-        A.status[b] = (int)osc[SV_STATUS];
     }
-    batch_copy<T, false>(sm, Qwg, nb * n * n, n, pitch, (int)per, tid);
-}
+};
 
 // One assess_optim per instance at x[B][n]: the same device function, without an ellipsoid.  keep_last: record the scan in
 // A.min_idx / A.min_val (the margins entry point looks without touching the oracle's state).  margins: [B][m] or null.
 template <int T>
-__global__ __launch_bounds__(T) void k_batch_svm_assess(long long B, int n, int epw, int m, long long ld, int keep_last,
-                                                        BatchSvmArrays A, const double* __restrict__ x,
-                                                        double* __restrict__ gamma_out, double* __restrict__ grad_out,
-                                                        double* __restrict__ beta_out, double* __restrict__ margins) {
+__global__ __launch_bounds__(T) void k_batch_svm_assess(long long B, int n, int epw, int keep_last, BatchSvmOracle::Args A,
+                                                        const double* __restrict__ x, double* __restrict__ gamma_out,
+                                                        double* __restrict__ grad_out, double* __restrict__ beta_out,
+                                                        double* __restrict__ margins) {
     extern __shared__ double sm[];
     const int tid = threadIdx.x;
     const int e = tid / n, i = tid - e * n;
@@ -287,18 +199,15 @@ __global__ __launch_bounds__(T) void k_batch_svm_assess(long long B, int n, int 
     if (active) {
         lx[i] = x[b * n + i];
         xt = A.XT + b * A.tab_stride;
-        lab = A.labels + b * (long long)m;
-        if (margins) mg = margins + b * (long long)m;
+        lab = A.labels + b * (long long)A.m;
+        if (margins) mg = margins + b * (long long)A.m;
     }
-    batch_svm_oracle(active, i, n, m, ld, xt, lab, lx, osc, g, mg);
+    batch_svm_oracle(active, i, n, A.m, A.ld, xt, lab, lx, osc, g, mg);
     if (active && grad_out) grad_out[b * n + i] = g[i];
     if (active && i == 0) {
         if (gamma_out) gamma_out[b] = osc[SV_GAMMA];
         if (beta_out) beta_out[b] = osc[SV_B0];
-        if (keep_last) {
-            A.min_idx[b] = (long long)osc[SV_MINIDX];
-            A.min_val[b] = osc[SV_MINVAL];
-        }
+        if (keep_last) BatchSvmOracle::store(A, b, osc, BatchSvmOracle::Regs{});
     }
 }
 

@@ -3038,6 +3038,7 @@ int ellhip_profile_read(ellhip_space* s, double* ms_out, int64_t* count_out) {
 #include "lmi_capi.inc.hpp"
 #include "sharded_capi.inc.hpp"
 #include "svm_capi.inc.hpp"
+#include "batch_loop_capi.inc.hpp"
 #include "batch_lmi_capi.inc.hpp"
 #include "batch_lowpass_capi.inc.hpp"
 #include "batch_svm_capi.inc.hpp"

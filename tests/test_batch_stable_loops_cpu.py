@@ -83,8 +83,11 @@ def test_sources_are_in_the_build_recipe():
     assert "ellhip_batch_stable_loops.h" in pkg.build.PUBLIC_HEADERS
     main = open(os.path.join(pkg.build.CSRC, "ellhip_capi.hip")).read()
     assert '#include "batch_stable_loops_capi.inc.hpp"' in main
+    # the three oracles reach the EllStable cut through the one loop kernel they are policies of
+    assert "batch_loop_kernels.hpp" in pkg.build.HEADERS and "batch_loop_capi.inc.hpp" in pkg.build.HEADERS
+    assert '#include "batch_stable_apply.hpp"' in open(os.path.join(pkg.build.CSRC, "batch_loop_kernels.hpp")).read()
     for kernels in ("batch_lmi_kernels.hpp", "batch_lowpass_kernels.hpp", "batch_svm_kernels.hpp"):
-        assert '#include "batch_stable_apply.hpp"' in open(os.path.join(pkg.build.CSRC, kernels)).read()
+        assert '#include "batch_loop_kernels.hpp"' in open(os.path.join(pkg.build.CSRC, kernels)).read()
 
 
 def test_lds_formula_of_the_header():

@@ -1,6 +1,6 @@
-// batch_lmi_split.hip -- how one round of k_batch_lmi_loop splits between the oracle and the ellipsoid update.
+// batch_lmi_split.hip -- how one round of k_batch_loop over the LMI oracle splits between the oracle and the ellipsoid update.
 //
-// A copy of the loop kernel (ellalgo-rs_amd/csrc/batch_lmi_kernels.hpp) with the constant 100 MHz wall clock read by
+// A copy of the loop kernel (ellalgo-rs_amd/csrc/batch_loop_kernels.hpp, optim only) with the constant 100 MHz wall clock read by
 // thread 0 of every workgroup before the oracle, between the oracle and the update, and after the update; each of
 // these points follows a barrier, so thread 0's clock is the workgroup's.  The oracle and the update themselves are the
 // product's device functions.  Problems: random strictly feasible pencils of the requested shape (F_jk symmetric normal,
@@ -32,7 +32,7 @@ using namespace ellhip;
     } while (0)
 
 template <int T, bool STABLE>
-__global__ __launch_bounds__(T) void k_loop_clocked(BatchParams P, BatchLmiParams L, BatchLmiLoop R, double* Q, double* xc,
+__global__ __launch_bounds__(T) void k_loop_clocked(BatchParams P, BatchLmiParams L, BatchLoopRun R, double* Q, double* xc,
                                                     double* kappa, const double* pencil, const double* matb,
                                                     const double* cvec, double* state /* [B][4]: gamma idx niter stopped */,
                                                     long long* clocks /* [grid][3]: oracle, update, rounds */,
@@ -68,8 +68,8 @@ __global__ __launch_bounds__(T) void k_loop_clocked(BatchParams P, BatchLmiParam
         sc[5] = 0.0;
         osc[LO_GAMMA] = state[b * 4 + 0];
         osc[LO_IDX] = state[b * 4 + 1];
-        osc[LO_NITER] = state[b * 4 + 2];
-        osc[LO_STOPPED] = state[b * 4 + 3];
+        osc[BL_NITER] = state[b * 4 + 2];
+        osc[BL_STOPPED] = state[b * 4 + 3];
     }
     __syncthreads();
     const bool lane_ok = tid < P.epw && b_first + tid < P.B;
@@ -81,14 +81,14 @@ __global__ __launch_bounds__(T) void k_loop_clocked(BatchParams P, BatchLmiParam
     const double shrunk_station = (double)(L.J + 1);
     long long t_oracle = 0, t_update = 0, rounds = 0;
     for (int it = 0; it < R.iters; ++it) {
-        const bool live = active && osc[LO_STOPPED] == 0.0;
+        const bool live = active && osc[BL_STOPPED] == 0.0;
         if (!__syncthreads_or(live)) break;
         if (live) lx[i] = xci;
         __syncthreads();
         const long long t0 = wall_clock64();
         batch_lmi_oracle(L, live, i, n, F, Bm, lx, cl, fa, wit, osc, g);
         const long long t1 = wall_clock64();
-        const bool lane = lane_ok && osc_s[LO_STOPPED] == 0.0;
+        const bool lane = lane_ok && osc_s[BL_STOPPED] == 0.0;
         const int kind = (lane && osc_s[LO_STATION] == shrunk_station) ? CUT_CENTRAL : CUT_BIAS;
         batch_space_cut_apply<STABLE>(P, calc, live, i, q, xci, lane, q_s, kind, lane ? osc_s[LO_BETA] : 0.0, 0, 0.0,
                                       [](int, double) {});
@@ -97,8 +97,8 @@ __global__ __launch_bounds__(T) void k_loop_clocked(BatchParams P, BatchLmiParam
         t_update += t2 - t1;
         rounds += 1;
         if (live && i == 0) {
-            if (sc[3] != 0.0 || sc[5] < R.tol) osc[LO_STOPPED] = 1.0;
-            else osc[LO_NITER] += 1.0;
+            if (sc[3] != 0.0 || sc[5] < R.tol) osc[BL_STOPPED] = 1.0;
+            else osc[BL_NITER] += 1.0;
         }
         __syncthreads();
     }
@@ -107,8 +107,8 @@ __global__ __launch_bounds__(T) void k_loop_clocked(BatchParams P, BatchLmiParam
         kappa[b] = sc[4];
         state[b * 4 + 0] = osc[LO_GAMMA];
         state[b * 4 + 1] = osc[LO_IDX];
-        state[b * 4 + 2] = osc[LO_NITER];
-        state[b * 4 + 3] = osc[LO_STOPPED];
+        state[b * 4 + 2] = osc[BL_NITER];
+        state[b * 4 + 3] = osc[BL_STOPPED];
     }
     if (tid == 0) {
         clocks[blockIdx.x * 3 + 0] += t_oracle;
@@ -193,7 +193,7 @@ int main(int argc, char** argv) {
     CHK(hipMemset(d_clk, 0, (size_t)grid * 3 * 8));
     CHK(hipDeviceSynchronize());
     BatchParams P{B, n, batch_pitch(n), epw, 0, 0};
-    BatchLmiLoop R{256, 0, 2000, tol};
+    BatchLoopRun R{256, 0, 2000, tol};
     const EllCalcDev calc = EllCalcDev::make(n, 1);
     auto kernel = T == 256 ? (stable ? &k_loop_clocked<256, true> : &k_loop_clocked<256, false>)
                            : (stable ? &k_loop_clocked<128, true> : &k_loop_clocked<128, false>);
