@@ -144,7 +144,8 @@ class EllStableBatch(_Batch):
 
 class EllBatchStreamed(EllBatch):
     """B `Ell` spaces of one dimension n <= 1024 with the matrices streamed from HBM (include/ellhip_batch_streamed.h):
-    the same calls and the same bits as `EllBatch`, past its n = 128.  The batched cutting-plane loops refuse it."""
+    the same calls and the same bits as `EllBatch`, past its n = 128.  Of the batched cutting-plane loops the low-pass one
+    runs on it (`BatchLowpassProblem.streamed`); the others refuse it."""
     _create = "ellhip_batch_create_streamed"
     _from_space = "ellhip_batch_streamed_from_space"
 

@@ -2,7 +2,8 @@
 independent `LowpassOracle`s (src/oracles/lowpass_oracle.rs) of one filter length n <= 128, each with its own band edges,
 ripple limits and round-robin cursors and its own ellipsoid of an `EllBatch` or an `EllStableBatch`
 (include/ellhip_batch_stable_loops.h), over one shared 15n x n table; solved by one kernel per chunk of iterations.
-Bit-identical to the CPU arithmetic."""
+`BatchLowpassProblem.streamed` (include/ellhip_batch_lowpass_streamed.h) takes n up to 1024 and solves on an
+`EllBatchStreamed`.  Bit-identical to the CPU arithmetic."""
 from __future__ import annotations
 
 import ctypes as C
@@ -16,8 +17,14 @@ STATE_INTS = ("more_alt", "idx1", "idx2", "idx3", "kmax", "nwpass", "nwstop")
 STATE_DOUBLES = ("fmax", "sp_sq")
 
 
+def _loop_entry(batch, name: str) -> str:
+    """the `_streamed` entry point for an EllBatchStreamed, else what capi.batch_loop_entry chooses"""
+    return name + "_streamed" if getattr(batch, "is_streamed", False) else capi.batch_loop_entry(batch, name)
+
+
 class BatchLowpassProblem:
-    def __init__(self, n: int, wpass, wstop, lp_sq, up_sq, sp_sq, spectrum=None, *, device: int = -1):
+    def __init__(self, n: int, wpass, wstop, lp_sq, up_sq, sp_sq, spectrum=None, *, device: int = -1,
+                 _create: str = "ellhip_batch_lowpass_create"):
         """wpass, wstop, lp_sq, up_sq, sp_sq: [B] each (scalars are broadcast to the longest); spectrum: the shared
         (15 n) x n table or None to have it computed as the reference does."""
         self._lib = capi.load()
@@ -27,10 +34,16 @@ class BatchLowpassProblem:
         n = int(n)
         spectrum = None if spectrum is None else _f64(spectrum, 15 * n * n)
         h = C.c_void_p()
-        capi.check(self._lib.ellhip_batch_lowpass_create(C.byref(h), B, n, *[_p(a) for a in arrs], _p(spectrum), device),
-                   "ellhip_batch_lowpass_create")
+        capi.check(getattr(self._lib, _create)(C.byref(h), B, n, *[_p(a) for a in arrs], _p(spectrum), device), _create)
         self._h = h
         self.B, self.n = int(B), n
+
+    @classmethod
+    def streamed(cls, n: int, wpass, wstop, lp_sq, up_sq, sp_sq, spectrum=None, *, device: int = -1):
+        """The same problems for 1 <= n <= 1024 (include/ellhip_batch_lowpass_streamed.h): `optim` / `feas` then take an
+        `EllBatchStreamed`.  The table is kept twice in HBM, 2 * 15 n^2 * 8 bytes: 240 MiB at n = 1024."""
+        return cls(n, wpass, wstop, lp_sq, up_sq, sp_sq, spectrum, device=device,
+                   _create="ellhip_batch_lowpass_create_streamed")
 
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None
@@ -89,14 +102,14 @@ class BatchLowpassProblem:
         return grad, beta0, has1, beta1, shrunk, gamma, rc
 
     def optim(self, batch, gamma, max_iters: int, tol: float):
-        """cutting_plane_optim per problem on `batch` (an EllBatch or an EllStableBatch).  Returns (x_best [B][n] with NaN
-        rows where there is none, has_best [B], niter [B], gamma [B], status [B])."""
+        """cutting_plane_optim per problem on `batch` (an EllBatch, an EllStableBatch or an EllBatchStreamed).  Returns
+        (x_best [B][n] with NaN rows where there is none, has_best [B], niter [B], gamma [B], status [B])."""
         gamma = np.array(np.broadcast_to(np.asarray(gamma, dtype=np.float64), (self.B,)))
         x_best = np.full((self.B, self.n), np.nan)
         has = np.empty(self.B, dtype=np.int32)
         niter = np.empty(self.B, dtype=np.int64)
         status = np.empty(self.B, dtype=np.int32)
-        entry = capi.batch_loop_entry(batch, "ellhip_batch_lowpass_optim")
+        entry = _loop_entry(batch, "ellhip_batch_lowpass_optim")
         capi.check(getattr(self._lib, entry)(batch._h, self._h, _p(gamma), int(max_iters), float(tol), _p(x_best), _p(has),
                                              _p(niter), _p(status)), entry)
         return x_best, has, niter, gamma, status
@@ -108,7 +121,7 @@ class BatchLowpassProblem:
         ok = np.empty(self.B, dtype=np.int32)
         niter = np.empty(self.B, dtype=np.int64)
         status = np.empty(self.B, dtype=np.int32)
-        entry = capi.batch_loop_entry(batch, "ellhip_batch_lowpass_feas")
+        entry = _loop_entry(batch, "ellhip_batch_lowpass_feas")
         capi.check(getattr(self._lib, entry)(batch._h, self._h, int(max_iters), float(tol), _p(x), _p(ok), _p(niter),
                                              _p(status)), entry)
         return x, ok, niter, status

@@ -174,48 +174,28 @@ struct BatchLoopWords {
     const char* n_is;   // "" or how the oracle's n comes about
 };
 
-// cutting_plane_optim (feas = 0, gamma in and out) or cutting_plane_feas for every instance: up to max_iters rounds in
-// launches of st.chunk, until every instance has stopped.
-// stable: the spaces are EllStable (include/ellhip_batch_stable_loops.h).  The caller has checked its pointers.
-template <class Oracle>
-int batch_loop_run(ellhip_batch* s, BatchLoopBuffers& st, const typename Oracle::Args& A,
-                   const BatchLoopWords& w, bool stable, int feas, double* gamma_inout, int64_t max_iters, double tol,
-                   double* x_out, int32_t* has_out, int64_t* niter_out, int32_t* status_out) {
-    const std::string what(w.what);
-    if (const int rc = batch_loop_check(s, stable, w.what)) return rc;
-    if (s->B != st.B || s->n != st.n)
-        return fail(ELLHIP_E_INVALID, (what + ": spaces and oracle differ in B or n" + w.n_is).c_str());
-    if (s->device != st.device) return fail(ELLHIP_E_INVALID, (what + ": spaces and oracle live on different devices").c_str());
+// The part of a run that does not depend on the kernel: cutting_plane_optim (feas = 0, gamma in and out) or
+// cutting_plane_feas for every instance, up to max_iters rounds in launches of st.chunk until every instance has stopped,
+// then the results.  launch(R) enqueues one launch of R.iters rounds on s->stream and returns 0 or an error code.  The
+// caller has checked that the spaces and the oracle fit each other.
+template <class Launch>
+int batch_loop_drive(ellhip_batch* s, BatchLoopBuffers& st, int feas, double* gamma_inout, int64_t max_iters, double tol,
+                     double* x_out, int32_t* has_out, int64_t* niter_out, int32_t* status_out, Launch launch) {
     if (max_iters < 0) return fail(ELLHIP_E_INVALID, "max_iters must be >= 0");
     const size_t B = (size_t)st.B, n = (size_t)st.n;
-    const BatchLoopShape sh = batch_loop_shape(s, stable);
-    const size_t lds = (size_t)sh.epw * (sh.space_doubles + Oracle::lds_doubles(A, s->n)) * sizeof(double);
-    if (lds > BATCH_LOOP_LDS_MAX)
-        return fail(ELLHIP_E_INVALID, (what + ": this " + w.shape + " needs more LDS than a workgroup has").c_str());
     DeviceGuard guard(s->device);
     const BatchLoopState S = batch_loop_view(st);
     HIPCHK(hipStreamSynchronize(s->stream));
     HIPCHK(hipStreamSynchronize(st.stream));
     HIPCHK(batch_loop_reset(st, s->stream));
     if (!feas) HIPCHK(hipMemcpy(st.d_gamma, gamma_inout, B * sizeof(double), hipMemcpyHostToDevice));
-    const BatchParams P = batch_loop_params(s, sh);
-    const EllCalcDev calc = EllCalcDev::make(s->n, s->use_parallel_cut);
     BatchLoopRun R;
     R.feas = feas;
     R.max_iters = max_iters;
     R.tol = tol;
     for (long long done = 0; done < max_iters; done += st.chunk) {
         R.iters = (int)std::min<long long>(st.chunk, max_iters - done);
-        int rc;
-        if (stable) {
-            rc = sh.T == 128 ? batch_loop_launch<128, true, Oracle>(s, sh, lds, P, R, S, A, calc)
-                             : batch_loop_launch<256, true, Oracle>(s, sh, lds, P, R, S, A, calc);
-        } else {
-            rc = sh.T == 64    ? batch_loop_launch<64, false, Oracle>(s, sh, lds, P, R, S, A, calc)
-                 : sh.T == 128 ? batch_loop_launch<128, false, Oracle>(s, sh, lds, P, R, S, A, calc)
-                               : batch_loop_launch<256, false, Oracle>(s, sh, lds, P, R, S, A, calc);
-        }
-        if (rc) return rc;
+        if (const int rc = launch(R)) return rc;
         HIPCHK(hipGetLastError());
         int nstopped = 0;
         HIPCHK(hipMemcpyAsync(&nstopped, S.nstopped, sizeof(int), hipMemcpyDeviceToHost, s->stream));
@@ -239,6 +219,35 @@ int batch_loop_run(ellhip_batch* s, BatchLoopBuffers& st, const typename Oracle:
             if (has[b]) memcpy(x_out + b * n, xb.data() + b * n, n * sizeof(double));
     }
     return 0;
+}
+
+// The loops on the LDS engine: k_batch_loop over a batch handle of Ell spaces, or of EllStable spaces (stable:
+// include/ellhip_batch_stable_loops.h).  The caller has checked its pointers.
+template <class Oracle>
+int batch_loop_run(ellhip_batch* s, BatchLoopBuffers& st, const typename Oracle::Args& A,
+                   const BatchLoopWords& w, bool stable, int feas, double* gamma_inout, int64_t max_iters, double tol,
+                   double* x_out, int32_t* has_out, int64_t* niter_out, int32_t* status_out) {
+    const std::string what(w.what);
+    if (const int rc = batch_loop_check(s, stable, w.what)) return rc;
+    if (s->B != st.B || s->n != st.n)
+        return fail(ELLHIP_E_INVALID, (what + ": spaces and oracle differ in B or n" + w.n_is).c_str());
+    if (s->device != st.device) return fail(ELLHIP_E_INVALID, (what + ": spaces and oracle live on different devices").c_str());
+    const BatchLoopShape sh = batch_loop_shape(s, stable);
+    const size_t lds = (size_t)sh.epw * (sh.space_doubles + Oracle::lds_doubles(A, s->n)) * sizeof(double);
+    if (lds > BATCH_LOOP_LDS_MAX)
+        return fail(ELLHIP_E_INVALID, (what + ": this " + w.shape + " needs more LDS than a workgroup has").c_str());
+    const BatchParams P = batch_loop_params(s, sh);
+    const EllCalcDev calc = EllCalcDev::make(s->n, s->use_parallel_cut);
+    const BatchLoopState S = batch_loop_view(st);
+    return batch_loop_drive(s, st, feas, gamma_inout, max_iters, tol, x_out, has_out, niter_out, status_out,
+                            [&](const BatchLoopRun& R) {
+        if (stable)
+            return sh.T == 128 ? batch_loop_launch<128, true, Oracle>(s, sh, lds, P, R, S, A, calc)
+                               : batch_loop_launch<256, true, Oracle>(s, sh, lds, P, R, S, A, calc);
+        return sh.T == 64    ? batch_loop_launch<64, false, Oracle>(s, sh, lds, P, R, S, A, calc)
+               : sh.T == 128 ? batch_loop_launch<128, false, Oracle>(s, sh, lds, P, R, S, A, calc)
+                             : batch_loop_launch<256, false, Oracle>(s, sh, lds, P, R, S, A, calc);
+    });
 }
 
 }  // namespace

@@ -78,9 +78,12 @@ int batch_lowpass_assess(ellhip_batch_lowpass* o, int optim, const double* x, do
     DeviceGuard guard(o->loop.device);
     const size_t B = (size_t)o->B, n = (size_t)o->n;
     const size_t per = batch_lowpass_lds_doubles(o->n) + n;
+    // past the LDS engine's n (batch_row_shape has no instance per workgroup to offer): one instance per workgroup, n threads
+    // rounded up to whole waves, as the streamed engine shapes its own
+    const bool wide = o->n > BATCH_NMAX;
     const BatchRowShape sh = batch_row_shape(o->n, per);
-    const int T = sh.T, epw = sh.epw;
-    const size_t lds = (size_t)epw * per * sizeof(double);  // at most 64 * 29 * 8 bytes
+    const int T = wide ? (o->n + 63) / 64 * 64 : sh.T, epw = wide ? 1 : sh.epw;
+    const size_t lds = (size_t)epw * per * sizeof(double);  // at most 64 * 29 * 8 bytes, or 16.2 KiB at n = 1024
     const unsigned grid = (unsigned)((o->B + epw - 1) / epw);
     double* d_beta0 = o->d_beta;
     double* d_beta1 = o->d_beta + B;
@@ -90,9 +93,10 @@ int batch_lowpass_assess(ellhip_batch_lowpass* o, int optim, const double* x, do
     HIPCHK(hipMemcpy(o->d_x, x, B * n * sizeof(double), hipMemcpyHostToDevice));
     if (optim) HIPCHK(hipMemcpy(o->loop.d_gamma, gamma_inout, B * sizeof(double), hipMemcpyHostToDevice));
 #define BATCH_LP_ASSESS(TT)                                                                                            \
-    hipLaunchKernelGGL(k_batch_lowpass_assess<TT>, dim3(grid), dim3(TT), lds, o->loop.stream, o->B, o->n, epw, optim,  \
+    hipLaunchKernelGGL(k_batch_lowpass_assess<TT>, dim3(grid), dim3(T), lds, o->loop.stream, o->B, o->n, epw, optim,   \
                        A, o->loop.d_gamma, (const double*)o->d_x, o->d_grad, d_beta0, d_hb1, d_beta1, d_ans)
-    if (T == 128) BATCH_LP_ASSESS(128);
+    if (wide) BATCH_LP_ASSESS(1024);  // (the template argument bounds the block; the block is T threads)
+    else if (T == 128) BATCH_LP_ASSESS(128);
     else BATCH_LP_ASSESS(256);
 #undef BATCH_LP_ASSESS
     HIPCHK(hipGetLastError());
@@ -116,16 +120,14 @@ int batch_lowpass_assess(ellhip_batch_lowpass* o, int optim, const double* x, do
     return 0;
 }
 
-}  // namespace
-
-extern "C" {
-
-int ellhip_batch_lowpass_create(ellhip_batch_lowpass** out, int64_t B, int64_t n, const double* wpass, const double* wstop,
-                                const double* lp_sq, const double* up_sq, const double* sp_sq, const double* spectrum,
-                                int device) {
+// nmax: 128 for the LDS engine's constructor, 1024 for the streamed one (batch_streamed_loop_capi.inc.hpp)
+int batch_lowpass_create(ellhip_batch_lowpass** out, int64_t B, int64_t n, const double* wpass, const double* wstop,
+                         const double* lp_sq, const double* up_sq, const double* sp_sq, const double* spectrum, int device,
+                         int nmax) {
     if (!out) return fail(ELLHIP_E_INVALID, "out is NULL");
     *out = nullptr;
-    if (B < 1 || n < 1 || n > BATCH_NMAX) return fail(ELLHIP_E_INVALID, "batched lowpass: need B >= 1 and 1 <= n <= 128");
+    if (B < 1 || n < 1 || n > nmax)
+        return fail(ELLHIP_E_INVALID, ("batched lowpass: need B >= 1 and 1 <= n <= " + std::to_string(nmax)).c_str());
     if (B > (1 << 24)) return fail(ELLHIP_E_INVALID, "batched lowpass: B too large");
     if (!wpass || !wstop || !lp_sq || !up_sq || !sp_sq) return fail(ELLHIP_E_INVALID, "NULL argument");
     const long long mdim = 15 * n;  //                                      src/oracles/lowpass_oracle.rs:24
@@ -194,6 +196,16 @@ int ellhip_batch_lowpass_create(ellhip_batch_lowpass** out, int64_t B, int64_t n
     if (rc) return bail(rc);
     *out = o;
     return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ellhip_batch_lowpass_create(ellhip_batch_lowpass** out, int64_t B, int64_t n, const double* wpass, const double* wstop,
+                                const double* lp_sq, const double* up_sq, const double* sp_sq, const double* spectrum,
+                                int device) {
+    return batch_lowpass_create(out, B, n, wpass, wstop, lp_sq, up_sq, sp_sq, spectrum, device, BATCH_NMAX);
 }
 
 void ellhip_batch_lowpass_destroy(ellhip_batch_lowpass* o) {

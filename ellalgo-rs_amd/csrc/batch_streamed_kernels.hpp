@@ -93,9 +93,58 @@ __device__ __forceinline__ double bs_product(const double* __restrict__ p, const
     return acc;
 }
 
+// The scalar stage of one cut, by one lane: omega, tsq, the cut's coefficients, and what the centre, the rank-1 and kappa
+// take from them.  sc: [0] rho/omega  [1] sigma/omega  [2] scale  [3] status  [4] kappa  [5] tsq; pr[j] = g[j] * gt[j].
+__device__ __forceinline__ int bs_scalar_stage(double* sc, const double* pr, const int n, const int no_defer_trick,
+                                               const EllCalcDev& calc, const int kind, const double b0, const int hb1,
+                                               const double b1) {
+    double omega = 0.0;  //                                                                                src/ell.rs:103
+    for (int j = 0; j < n; ++j) omega += pr[j];
+    const double kap = sc[4];
+    const double t = kap * omega;  //                                                                      :105
+    Coef cf;
+    const int st = calc.dispatch(kind, b0, hb1, b1, t, cf);  //                                            :106
+    sc[5] = t;
+    sc[3] = (double)st;
+    if (st == ST_SUCCESS) {
+        sc[0] = cf.rho / omega;    //                                                                      :112
+        sc[1] = cf.sigma / omega;  //                                                                      :117
+        const double knew = kap * cf.delta;  //                                                            :130
+        if (no_defer_trick) {      //                                                                      :132-135
+            sc[2] = knew;
+            sc[4] = 1.0;
+        } else {
+            sc[2] = 1.0;
+            sc[4] = knew;
+        }
+    }
+    return st;
+}
+
+// The rank-1 of a successful cut on a matrix that is not symmetric yet (a matrix from the caller before its first successful
+// cut): the lower triangle and the diagonal update themselves, then the upper triangle is their mirror image (:119-128).
+// Collective: one barrier inside.
+__device__ __forceinline__ void bs_sweep_mirror(double* Qb, const int n, const int i, const bool active,
+                                                const double* gt, const double* sg, const bool scaled, const double scale) {
+    double* col = Qb + (active ? i : 0);
+    if (active) {
+        const double gti = gt[i];
+        for (int r = i; r < n; ++r) {
+            double v = col[(size_t)r * n] - sg[r] * gti;
+            if (scaled) v = v * scale;
+            col[(size_t)r * n] = v;
+        }
+    }
+    __syncthreads();  // the workgroup's own stores to Qb are visible to its loads after the barrier
+    if (active) {
+        const double* row = Qb + (size_t)i * n;
+        for (int r = 0; r < i; ++r) col[(size_t)r * n] = row[r];
+    }
+}
+
 // Cut k of ellipsoid b: kinds / beta arrays are [K][B], grads [K][B][n]; status / tsq outputs [K][B].  One workgroup per
 // ellipsoid, blockDim.x = n rounded up to a multiple of 64, dynamic LDS = batch_streamed_lds_doubles(n) doubles.  One
-// instantiation for every n: bounded for 1024 threads it needs 75 VGPRs, fewer than a variant bounded for 256 was given.
+// instantiation for every n: bounded for 1024 threads it needs 73 VGPRs, fewer than a variant bounded for 256 was given.
 __global__ __launch_bounds__(1024) void k_batch_streamed_update(
     BatchStreamedParams P, double* __restrict__ Q, double* __restrict__ xc, double* __restrict__ kappa,
     double* __restrict__ tsq, int* __restrict__ sym, const int* __restrict__ kinds, const double* __restrict__ grads,
@@ -142,28 +191,9 @@ __global__ __launch_bounds__(1024) void k_batch_streamed_update(
         }
         __syncthreads();
         if (i == 0) {
-            double omega = 0.0;  //                                                                        src/ell.rs:103
-            for (int j = 0; j < n; ++j) omega += pr[j];
-            const double kap = sc[4];
-            const double t = kap * omega;  //                                                              :105
-            Coef cf;
-            const int st = calc.dispatch(kinds[cut], beta0[cut], has_b1[cut], beta1[cut], t, cf);  //      :106
-            sc[5] = t;
-            sc[3] = (double)st;
-            if (st == ST_SUCCESS) {
-                sc[0] = cf.rho / omega;    //                                                              :112
-                sc[1] = cf.sigma / omega;  //                                                              :117
-                const double knew = kap * cf.delta;  //                                                    :130
-                if (P.no_defer_trick) {    //                                                              :132-135
-                    sc[2] = knew;
-                    sc[4] = 1.0;
-                } else {
-                    sc[2] = 1.0;
-                    sc[4] = knew;
-                }
-            }
+            const int st = bs_scalar_stage(sc, pr, n, P.no_defer_trick, calc, kinds[cut], beta0[cut], has_b1[cut], beta1[cut]);
             status_out[cut] = st;
-            if (tsq_out) tsq_out[cut] = t;
+            if (tsq_out) tsq_out[cut] = sc[5];
         }
         __syncthreads();
         const bool ok = sc[3] == (double)ST_SUCCESS;
@@ -183,21 +213,7 @@ __global__ __launch_bounds__(1024) void k_batch_streamed_update(
                 }
                 have_gt = more;
             } else {
-                // not symmetric yet (a matrix from the caller before its first successful cut): the lower triangle and the
-                // diagonal update themselves, then the upper triangle is their mirror image                 :119-128
-                if (active) {
-                    const double gti = gt[i];
-                    for (int r = i; r < n; ++r) {
-                        double v = col[(size_t)r * n] - sg[r] * gti;
-                        if (scaled) v = v * scale;
-                        col[(size_t)r * n] = v;
-                    }
-                }
-                __syncthreads();  // the workgroup's own stores to Qb are visible to its loads after the barrier
-                if (active) {
-                    const double* row = Qb + (size_t)i * n;
-                    for (int r = 0; r < i; ++r) col[(size_t)r * n] = row[r];
-                }
+                bs_sweep_mirror(Qb, n, i, active, gt, sg, scaled, scale);
                 if (i == 0) sc[6] = 1.0;
             }
         }

@@ -2,7 +2,8 @@
 // the device (include/ellhip_batch_lowpass.h): the C++ counterpart of
 //     for b in 0..B { cutting_plane_optim(&mut omega[b], &mut space[b], &mut gamma[b], &options) }
 // with omega[b] a LowpassOracle (src/oracles/lowpass_oracle.rs:7-151) of its own band edges and ripple limits and
-// space[b] the b-th ellipsoid of an EllBatchHip.  Bit-identical to the CPU arithmetic.
+// space[b] the b-th ellipsoid of an EllBatchHip.  Bit-identical to the CPU arithmetic.  BatchLowpassHip::streamed
+// (include/ellhip_batch_lowpass_streamed.h) takes filter lengths up to 1024 and solves on an EllBatchStreamedHip.
 #pragma once
 
 #include <cstdint>
@@ -10,6 +11,7 @@
 #include <utility>
 #include <vector>
 
+#include "../../../include/ellhip_batch_lowpass_streamed.h"
 #include "../../../include/ellhip_batch_stable_loops.h"
 #include "ell_batch_hip.hpp"
 
@@ -38,20 +40,11 @@ class BatchLowpassHip {
 
     // spectrum: empty = computed as the reference does; else the shared table, row-major 15 ndim x ndim
     BatchLowpassHip(std::size_t ndim, const std::vector<LowpassSpec>& specs, const Arr& spectrum = Arr(), int device = -1)
-        : B_(specs.size()), n_(ndim) {
-        if (specs.empty()) throw Error(ELLHIP_E_INVALID, "need at least one problem");
-        if (!spectrum.empty() && spectrum.size() != 15 * ndim * ndim) throw Error(ELLHIP_E_INVALID, "spectrum must be 15n x n");
-        Arr wp, ws, lp, up, sp;
-        for (const LowpassSpec& s : specs) {
-            wp.push_back(s.wpass);
-            ws.push_back(s.wstop);
-            lp.push_back(s.lp_sq);
-            up.push_back(s.up_sq);
-            sp.push_back(s.sp_sq);
-        }
-        check(ellhip_batch_lowpass_create(&h_, (int64_t)B_, (int64_t)n_, wp.data(), ws.data(), lp.data(), up.data(),
-                                          sp.data(), spectrum.empty() ? nullptr : spectrum.data(), device),
-              "ellhip_batch_lowpass_create");
+        : BatchLowpassHip(ndim, specs, spectrum, device, false) {}
+    // the same problems for ndim up to 1024: optim / feas then take an EllBatchStreamedHip
+    static BatchLowpassHip streamed(std::size_t ndim, const std::vector<LowpassSpec>& specs, const Arr& spectrum = Arr(),
+                                    int device = -1) {
+        return BatchLowpassHip(ndim, specs, spectrum, device, true);
     }
     BatchLowpassHip(const BatchLowpassHip&) = delete;
     BatchLowpassHip& operator=(const BatchLowpassHip&) = delete;
@@ -92,31 +85,36 @@ class BatchLowpassHip {
         return r;
     }
     // cutting_plane_optim (src/cutting_plane.rs:286-313) for every problem; gamma has B entries and is updated
-    // (spaces: an EllBatchHip, or an EllStableBatchHip through include/ellhip_batch_stable_loops.h)
-    template <int VARIANT>
-    BatchLowpassResult optim(BatchHip<VARIANT>& spaces, Arr& gamma, const Options& options) {
+    // (spaces: an EllBatchHip, an EllStableBatchHip through include/ellhip_batch_stable_loops.h, or an EllBatchStreamedHip
+    // through include/ellhip_batch_lowpass_streamed.h)
+    template <int VARIANT, bool STREAMED>
+    BatchLowpassResult optim(BatchHip<VARIANT, STREAMED>& spaces, Arr& gamma, const Options& options) {
         constexpr bool stable = VARIANT == ELLHIP_SPACE_ELL_STABLE;
         if (gamma.size() != B_) throw Error(ELLHIP_E_INVALID, "gamma must have B entries");
         Arr x(B_ * n_);
         std::vector<int32_t> has(B_), status(B_);
         std::vector<int64_t> niter(B_);
-        check((stable ? ellhip_batch_lowpass_optim_stable : ellhip_batch_lowpass_optim)(
-                  spaces.handle(), h_, gamma.data(), (int64_t)options.max_iters, options.tolerance, x.data(), has.data(),
-                  niter.data(), status.data()),
-              stable ? "ellhip_batch_lowpass_optim_stable" : "ellhip_batch_lowpass_optim");
+        const auto entry = STREAMED ? ellhip_batch_lowpass_optim_streamed
+                           : stable ? ellhip_batch_lowpass_optim_stable
+                                    : ellhip_batch_lowpass_optim;
+        check(entry(spaces.handle(), h_, gamma.data(), (int64_t)options.max_iters, options.tolerance, x.data(), has.data(),
+                    niter.data(), status.data()),
+              STREAMED ? "ellhip_batch_lowpass_optim_streamed" : stable ? "ellhip_batch_lowpass_optim_stable" : "ellhip_batch_lowpass_optim");
         return result(x, has, niter, status);
     }
     // cutting_plane_feas (:205-227) for every problem
-    template <int VARIANT>
-    BatchLowpassResult feas(BatchHip<VARIANT>& spaces, const Options& options) {
+    template <int VARIANT, bool STREAMED>
+    BatchLowpassResult feas(BatchHip<VARIANT, STREAMED>& spaces, const Options& options) {
         constexpr bool stable = VARIANT == ELLHIP_SPACE_ELL_STABLE;
         Arr x(B_ * n_);
         std::vector<int32_t> has(B_), status(B_);
         std::vector<int64_t> niter(B_);
-        check((stable ? ellhip_batch_lowpass_feas_stable : ellhip_batch_lowpass_feas)(
-                  spaces.handle(), h_, (int64_t)options.max_iters, options.tolerance, x.data(), has.data(), niter.data(),
-                  status.data()),
-              stable ? "ellhip_batch_lowpass_feas_stable" : "ellhip_batch_lowpass_feas");
+        const auto entry = STREAMED ? ellhip_batch_lowpass_feas_streamed
+                           : stable ? ellhip_batch_lowpass_feas_stable
+                                    : ellhip_batch_lowpass_feas;
+        check(entry(spaces.handle(), h_, (int64_t)options.max_iters, options.tolerance, x.data(), has.data(), niter.data(),
+                    status.data()),
+              STREAMED ? "ellhip_batch_lowpass_feas_streamed" : stable ? "ellhip_batch_lowpass_feas_stable" : "ellhip_batch_lowpass_feas");
         return result(x, has, niter, status);
     }
     std::vector<Fields> fields() const {
@@ -140,6 +138,23 @@ class BatchLowpassHip {
     ellhip_batch_lowpass* handle() { return h_; }
 
   private:
+    BatchLowpassHip(std::size_t ndim, const std::vector<LowpassSpec>& specs, const Arr& spectrum, int device, bool streamed)
+        : B_(specs.size()), n_(ndim) {
+        if (specs.empty()) throw Error(ELLHIP_E_INVALID, "need at least one problem");
+        if (!spectrum.empty() && spectrum.size() != 15 * ndim * ndim) throw Error(ELLHIP_E_INVALID, "spectrum must be 15n x n");
+        Arr wp, ws, lp, up, sp;
+        for (const LowpassSpec& s : specs) {
+            wp.push_back(s.wpass);
+            ws.push_back(s.wstop);
+            lp.push_back(s.lp_sq);
+            up.push_back(s.up_sq);
+            sp.push_back(s.sp_sq);
+        }
+        check((streamed ? ellhip_batch_lowpass_create_streamed : ellhip_batch_lowpass_create)(
+                  &h_, (int64_t)B_, (int64_t)n_, wp.data(), ws.data(), lp.data(), up.data(), sp.data(),
+                  spectrum.empty() ? nullptr : spectrum.data(), device),
+              streamed ? "ellhip_batch_lowpass_create_streamed" : "ellhip_batch_lowpass_create");
+    }
     Arr flatten(const std::vector<Arr>& x) const {
         if (x.size() != B_) throw Error(ELLHIP_E_INVALID, "x must have B rows");
         Arr flat;

@@ -12,8 +12,9 @@
  * _set_use_parallel_cut, _destroy) works on it with unchanged semantics, and ellhip_batch_get_mq returns each matrix
  * exactly as the reference would hold it (before the first successful cut that includes a non-symmetric upper triangle).
  * Every step follows the reference's statement order, so the results are bit-identical to the CPU arithmetic and to the
- * LDS engine.  The batched cutting-plane loops (ellhip_batch_{lmi,lowpass,svm}_* and their _stable forms) refuse a
- * streamed handle with ELLHIP_E_INVALID at every n: their kernels assume the LDS layout.
+ * LDS engine.  The batched cutting-plane loops of ellhip_batch_{lmi,lowpass,svm}.h and their _stable forms refuse a
+ * streamed handle with ELLHIP_E_INVALID at every n: their kernel assumes the LDS layout.  The low-pass design loop has
+ * entry points of its own for a streamed handle, ellhip_batch_lowpass_{optim,feas}_streamed (ellhip_batch_lowpass_streamed.h).
  *
  * Traffic per ellipsoid, what the kernel moves: the first cut of a launch, or a cut that follows a failed one, reads the
  * matrix once for Q g (8 n^2 bytes) and a successful cut reads and writes it once more for the rank-1 update (16 n^2);
