@@ -16,6 +16,7 @@ struct ellhip_batch {
     size_t lds_bytes = 0;
     int no_defer_trick = 0;
     int use_parallel_cut = 1;
+    Allocs mem;
     int streamed = 0;      // made by ellhip_batch_create_streamed / _streamed_from_space: k_batch_streamed_update, Q stays in HBM
     int* d_sym = nullptr;  // streamed only: [B], 1 = that matrix is symmetric to the bit (batch_streamed_kernels.hpp)
     double* d_Q = nullptr;
@@ -30,10 +31,10 @@ namespace {
 int batch_alloc(ellhip_batch* h) {
     const size_t B = (size_t)h->B, n = (size_t)h->n;
     HIPCHK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-    HIPCHK(hipMalloc(&h->d_Q, B * n * n * sizeof(double)));
-    HIPCHK(hipMalloc(&h->d_xc, B * n * sizeof(double)));
-    HIPCHK(hipMalloc(&h->d_kappa, B * sizeof(double)));
-    HIPCHK(hipMalloc(&h->d_tsq, B * sizeof(double)));
+    HIPCHK(h->mem.device(h->d_Q, B * n * n * sizeof(double)));
+    HIPCHK(h->mem.device(h->d_xc, B * n * sizeof(double)));
+    HIPCHK(h->mem.device(h->d_kappa, B * sizeof(double)));
+    HIPCHK(h->mem.device(h->d_tsq, B * sizeof(double)));
     HIPCHK(fill_now(h->d_tsq, 0, B * sizeof(double), h->stream));
     return 0;
 }
@@ -158,7 +159,7 @@ int batch_new(ellhip_batch** out, long long B, long long n, int device, int vari
     DeviceGuard guard(device);
     int rc = batch_shape(h);
     if (!rc) rc = batch_alloc(h);
-    if (!rc && streamed && hipMalloc(&h->d_sym, (size_t)B * sizeof(int)) != hipSuccess)
+    if (!rc && streamed && h->mem.device(h->d_sym, (size_t)B * sizeof(int)) != hipSuccess)
         rc = fail(ELLHIP_E_NOMEM, "streamed batch engine: flags");
     if (rc) {
         ellhip_batch_destroy(h);
@@ -183,9 +184,10 @@ int batch_create(ellhip_batch** out, int64_t B, int64_t n, const double* kappa, 
     if (mq) {
         e = hipMemcpy(h->d_Q, mq, sB * sn * sn * sizeof(double), hipMemcpyHostToDevice);
     } else {
+        Allocs tmp;
         double* d_diag = nullptr;
         if (diag) {
-            e = hipMalloc(&d_diag, sB * sn * sizeof(double));
+            e = tmp.device(d_diag, sB * sn * sizeof(double));
             if (e == hipSuccess) e = hipMemcpy(d_diag, diag, sB * sn * sizeof(double), hipMemcpyHostToDevice);
         }
         if (e == hipSuccess) {
@@ -194,7 +196,6 @@ int batch_create(ellhip_batch** out, int64_t B, int64_t n, const double* kappa, 
             e = hipGetLastError();
             if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
         }
-        if (d_diag) (void)hipFree(d_diag);
     }
     if (e != hipSuccess) return bail(fail(ELLHIP_E_HIP, "batch create: matrix", e));
     if (xc) e = hipMemcpy(h->d_xc, xc, sB * sn * sizeof(double), hipMemcpyHostToDevice);
@@ -288,11 +289,7 @@ void ellhip_batch_destroy(ellhip_batch* h) {
     if (!h) return;
     DeviceGuard guard(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    if (h->d_Q) (void)hipFree(h->d_Q);
-    if (h->d_xc) (void)hipFree(h->d_xc);
-    if (h->d_kappa) (void)hipFree(h->d_kappa);
-    if (h->d_tsq) (void)hipFree(h->d_tsq);
-    if (h->d_sym) (void)hipFree(h->d_sym);
+    h->mem.release_all();
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
 }
@@ -325,13 +322,14 @@ int ellhip_batch_update(ellhip_batch* h, int64_t K, const int32_t* kinds, const 
             }
     int *d_kinds = nullptr, *d_hb = nullptr, *d_status = nullptr;
     double *d_g = nullptr, *d_b0 = nullptr, *d_b1 = nullptr, *d_tsq = nullptr;
-    hipError_t e = hipMalloc(&d_kinds, KB * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc(&d_hb, KB * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc(&d_status, KB * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc(&d_g, KB * n * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc(&d_b0, KB * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc(&d_b1, KB * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc(&d_tsq, KB * sizeof(double));
+    Allocs tmp;  // (the seven staging buffers live for this call)
+    hipError_t e = tmp.device(d_kinds, KB * sizeof(int));
+    if (e == hipSuccess) e = tmp.device(d_hb, KB * sizeof(int));
+    if (e == hipSuccess) e = tmp.device(d_status, KB * sizeof(int));
+    if (e == hipSuccess) e = tmp.device(d_g, KB * n * sizeof(double));
+    if (e == hipSuccess) e = tmp.device(d_b0, KB * sizeof(double));
+    if (e == hipSuccess) e = tmp.device(d_b1, KB * sizeof(double));
+    if (e == hipSuccess) e = tmp.device(d_tsq, KB * sizeof(double));
     if (e == hipSuccess) e = hipMemcpy(d_kinds, kinds, KB * sizeof(int), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(d_hb, hb.data(), KB * sizeof(int), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(d_g, grads, KB * n * sizeof(double), hipMemcpyHostToDevice);
@@ -344,13 +342,7 @@ int ellhip_batch_update(ellhip_batch* h, int64_t K, const int32_t* kinds, const 
     }
     if (!rc && e == hipSuccess) e = hipMemcpy(status_out, d_status, KB * sizeof(int), hipMemcpyDeviceToHost);
     if (!rc && e == hipSuccess && tsq_out) e = hipMemcpy(tsq_out, d_tsq, KB * sizeof(double), hipMemcpyDeviceToHost);
-    (void)hipFree(d_kinds);
-    (void)hipFree(d_hb);
-    (void)hipFree(d_status);
-    (void)hipFree(d_g);
-    (void)hipFree(d_b0);
-    (void)hipFree(d_b1);
-    (void)hipFree(d_tsq);
+    tmp.release_all();
     if (rc) return rc;
     if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? ELLHIP_E_NOMEM : ELLHIP_E_HIP, "ellhip_batch_update", e);
     return 0;

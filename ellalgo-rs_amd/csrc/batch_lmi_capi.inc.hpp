@@ -105,13 +105,13 @@ int ellhip_batch_lmi_create(ellhip_batch_lmi** out, int64_t B, int64_t n, int64_
         src_b += sB * mm;
     }
     hipError_t e = batch_loop_alloc(o->loop, device, B, (int)n);
-    if (e == hipSuccess) e = hipMalloc(&o->d_pencil, pk.size() * sizeof(double));
-    if (e == hipSuccess && mat_b) e = hipMalloc(&o->d_matb, pb.size() * sizeof(double));
-    if (e == hipSuccess && c) e = hipMalloc(&o->d_c, sB * sn * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc(&o->d_idx, sB * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc(&o->d_x, sB * sn * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc(&o->d_grad, sB * sn * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc(&o->d_beta, sB * sizeof(double));
+    if (e == hipSuccess) e = o->loop.mem.device(o->d_pencil, pk.size() * sizeof(double));
+    if (e == hipSuccess && mat_b) e = o->loop.mem.device(o->d_matb, pb.size() * sizeof(double));
+    if (e == hipSuccess && c) e = o->loop.mem.device(o->d_c, sB * sn * sizeof(double));
+    if (e == hipSuccess) e = o->loop.mem.device(o->d_idx, sB * sizeof(int));
+    if (e == hipSuccess) e = o->loop.mem.device(o->d_x, sB * sn * sizeof(double));
+    if (e == hipSuccess) e = o->loop.mem.device(o->d_grad, sB * sn * sizeof(double));
+    if (e == hipSuccess) e = o->loop.mem.device(o->d_beta, sB * sizeof(double));
     if (e != hipSuccess) return bail(fail(e == hipErrorOutOfMemory ? ELLHIP_E_NOMEM : ELLHIP_E_HIP, "batched LMI allocation", e));
     e = hipMemcpy(o->d_pencil, pk.data(), pk.size() * sizeof(double), hipMemcpyHostToDevice);
     if (e == hipSuccess && mat_b) e = hipMemcpy(o->d_matb, pb.data(), pb.size() * sizeof(double), hipMemcpyHostToDevice);
@@ -126,9 +126,6 @@ void ellhip_batch_lmi_destroy(ellhip_batch_lmi* o) {
     if (!o) return;
     DeviceGuard guard(o->loop.device);
     batch_loop_free(o->loop);
-    void* bufs[] = {o->d_pencil, o->d_matb, o->d_c, o->d_idx, o->d_x, o->d_grad, o->d_beta};
-    for (void* p : bufs)
-        if (p) (void)hipFree(p);
     delete o;
 }
 

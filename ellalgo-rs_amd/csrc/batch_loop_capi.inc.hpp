@@ -8,8 +8,10 @@
 
 namespace {
 
-// The part of an oracle handle that every batched loop has: where the handle lives, its stream, and the loop state.
+// The part of an oracle handle that every batched loop has: where the handle lives, its stream, the loop state, and the
+// owner of ALL the handle's device memory (the oracle's own buffers too: one release in batch_loop_free).
 struct BatchLoopBuffers {
+    Allocs mem;
     int device = 0;
     long long B = 0;
     int n = 0;
@@ -28,10 +30,10 @@ hipError_t batch_loop_alloc(BatchLoopBuffers& st, int device, long long B, int n
     st.n = n;
     const size_t sB = (size_t)B, sn = (size_t)n;
     hipError_t e = hipStreamCreateWithFlags(&st.stream, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipMalloc(&st.d_gamma, sB * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc(&st.d_xbest, sB * sn * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc(&st.d_niter, sB * sizeof(long long));
-    if (e == hipSuccess) e = hipMalloc(&st.d_ints, (3 * sB + 1) * sizeof(int));
+    if (e == hipSuccess) e = st.mem.device(st.d_gamma, sB * sizeof(double));
+    if (e == hipSuccess) e = st.mem.device(st.d_xbest, sB * sn * sizeof(double));
+    if (e == hipSuccess) e = st.mem.device(st.d_niter, sB * sizeof(long long));
+    if (e == hipSuccess) e = st.mem.device(st.d_ints, (3 * sB + 1) * sizeof(int));
     if (e == hipSuccess) e = fill_now(st.d_gamma, 0, sB * sizeof(double), st.stream);
     if (e == hipSuccess) e = fill_now(st.d_xbest, 0, sB * sn * sizeof(double), st.stream);
     if (e == hipSuccess) e = fill_now(st.d_niter, 0, sB * sizeof(long long), st.stream);
@@ -46,14 +48,12 @@ hipError_t batch_loop_reset(BatchLoopBuffers& st, hipStream_t stream) {
     return e == hipSuccess ? fill_now(st.d_niter, 0, sB * sizeof(long long), stream) : e;
 }
 
-// waits for the stream; the caller has selected the device
+// waits for the stream, releases the handle's memory, then the stream; the caller has selected the device
 void batch_loop_free(BatchLoopBuffers& st) {
     if (st.stream) (void)hipStreamSynchronize(st.stream);
-    void* bufs[] = {st.d_gamma, st.d_xbest, st.d_niter, st.d_ints};
-    for (void* p : bufs)
-        if (p) (void)hipFree(p);
+    st.mem.release_all();
     if (st.stream) (void)hipStreamDestroy(st.stream);
-    st = BatchLoopBuffers{};
+    st.stream = nullptr;
 }
 
 BatchLoopState batch_loop_view(const BatchLoopBuffers& st) {

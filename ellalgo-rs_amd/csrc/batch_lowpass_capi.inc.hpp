@@ -170,18 +170,18 @@ int batch_lowpass_create(ellhip_batch_lowpass** out, int64_t B, int64_t n, const
     for (size_t r = 0; r < (size_t)mdim; ++r)
         for (size_t j = 0; j < sn; ++j) cols[j * (size_t)mdim + r] = rows[r * sn + j];
     hipError_t e = batch_loop_alloc(o->loop, device, B, (int)n);
-    if (e == hipSuccess) e = hipMalloc(&o->d_spec, tab * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc(&o->d_specT, tab * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc(&o->d_bands, 2 * sB * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc(&o->d_lims, 2 * sB * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc(&o->d_cursor, 4 * sB * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc(&o->d_kmax, sB * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc(&o->d_fmax, sB * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc(&o->d_spsq, sB * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc(&o->d_x, sB * sn * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc(&o->d_grad, sB * sn * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc(&o->d_beta, 2 * sB * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc(&o->d_aints, 2 * sB * sizeof(int));
+    if (e == hipSuccess) e = o->loop.mem.device(o->d_spec, tab * sizeof(double));
+    if (e == hipSuccess) e = o->loop.mem.device(o->d_specT, tab * sizeof(double));
+    if (e == hipSuccess) e = o->loop.mem.device(o->d_bands, 2 * sB * sizeof(int));
+    if (e == hipSuccess) e = o->loop.mem.device(o->d_lims, 2 * sB * sizeof(double));
+    if (e == hipSuccess) e = o->loop.mem.device(o->d_cursor, 4 * sB * sizeof(int));
+    if (e == hipSuccess) e = o->loop.mem.device(o->d_kmax, sB * sizeof(int));
+    if (e == hipSuccess) e = o->loop.mem.device(o->d_fmax, sB * sizeof(double));
+    if (e == hipSuccess) e = o->loop.mem.device(o->d_spsq, sB * sizeof(double));
+    if (e == hipSuccess) e = o->loop.mem.device(o->d_x, sB * sn * sizeof(double));
+    if (e == hipSuccess) e = o->loop.mem.device(o->d_grad, sB * sn * sizeof(double));
+    if (e == hipSuccess) e = o->loop.mem.device(o->d_beta, 2 * sB * sizeof(double));
+    if (e == hipSuccess) e = o->loop.mem.device(o->d_aints, 2 * sB * sizeof(int));
     if (e != hipSuccess)
         return bail(fail(e == hipErrorOutOfMemory ? ELLHIP_E_NOMEM : ELLHIP_E_HIP, "batched lowpass allocation", e));
     e = hipMemcpy(o->d_spec, rows.data(), tab * sizeof(double), hipMemcpyHostToDevice);
@@ -212,10 +212,6 @@ void ellhip_batch_lowpass_destroy(ellhip_batch_lowpass* o) {
     if (!o) return;
     DeviceGuard guard(o->loop.device);
     batch_loop_free(o->loop);
-    void* bufs[] = {o->d_spec, o->d_specT, o->d_bands, o->d_lims,  o->d_cursor, o->d_kmax,
-                    o->d_fmax, o->d_spsq,  o->d_x,     o->d_grad,  o->d_beta,   o->d_aints};
-    for (void* p : bufs)
-        if (p) (void)hipFree(p);
     delete o;
 }
 

@@ -44,7 +44,7 @@ int batch_svm_assess(ellhip_batch_svm* o, const double* x, int keep_last, double
     DeviceGuard guard(o->loop.device);
     const size_t B = (size_t)o->B, n = (size_t)o->n, m = (size_t)o->m;
     if (margins_out && !o->d_margins) {
-        const hipError_t e = hipMalloc(&o->d_margins, B * m * sizeof(double));
+        const hipError_t e = o->loop.mem.device(o->d_margins, B * m * sizeof(double));
         if (e != hipSuccess)
             return fail(e == hipErrorOutOfMemory ? ELLHIP_E_NOMEM : ELLHIP_E_HIP, "batched svm margins allocation", e);
     }
@@ -106,13 +106,13 @@ int ellhip_batch_svm_create(ellhip_batch_svm** out, int64_t B, int64_t m, int64_
     const size_t ntab = o->shared ? 1 : sB;
     const size_t tbytes = ntab * sf * (size_t)o->ld * sizeof(double);
     hipError_t e = batch_loop_alloc(o->loop, device, B, o->n);
-    if (e == hipSuccess) e = hipMalloc(&o->d_XT, tbytes);
-    if (e == hipSuccess) e = hipMalloc(&o->d_labels, sB * sm * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc(&o->d_minidx, sB * sizeof(long long));
-    if (e == hipSuccess) e = hipMalloc(&o->d_minval, sB * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc(&o->d_x, sB * sn * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc(&o->d_grad, sB * sn * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc(&o->d_beta, 2 * sB * sizeof(double));
+    if (e == hipSuccess) e = o->loop.mem.device(o->d_XT, tbytes);
+    if (e == hipSuccess) e = o->loop.mem.device(o->d_labels, sB * sm * sizeof(int));
+    if (e == hipSuccess) e = o->loop.mem.device(o->d_minidx, sB * sizeof(long long));
+    if (e == hipSuccess) e = o->loop.mem.device(o->d_minval, sB * sizeof(double));
+    if (e == hipSuccess) e = o->loop.mem.device(o->d_x, sB * sn * sizeof(double));
+    if (e == hipSuccess) e = o->loop.mem.device(o->d_grad, sB * sn * sizeof(double));
+    if (e == hipSuccess) e = o->loop.mem.device(o->d_beta, 2 * sB * sizeof(double));
     if (e != hipSuccess)
         return bail(fail(e == hipErrorOutOfMemory ? ELLHIP_E_NOMEM : ELLHIP_E_HIP, "batched svm allocation", e));
     // every fill is complete before anything else touches its buffer (fill_now waits)
@@ -129,8 +129,9 @@ int ellhip_batch_svm_create(ellhip_batch_svm** out, int64_t B, int64_t m, int64_
     // the device (peak device memory is the tables plus one slab; no host transpose)
     const long long total = (long long)ntab * m;
     const long long slab_rows = std::max<long long>(1, std::min<long long>(total, (64LL << 20) / (nfeat * 8)));
+    Allocs slab;  // (gone on every return path)
     double* d_slab = nullptr;
-    e = hipMalloc(&d_slab, (size_t)slab_rows * sf * sizeof(double));
+    e = slab.device(d_slab, (size_t)slab_rows * sf * sizeof(double));
     if (e != hipSuccess)
         return bail(fail(e == hipErrorOutOfMemory ? ELLHIP_E_NOMEM : ELLHIP_E_HIP, "batched svm staging allocation", e));
     for (long long r0 = 0; r0 < total && e == hipSuccess; r0 += slab_rows) {
@@ -144,7 +145,7 @@ int ellhip_batch_svm_create(ellhip_batch_svm** out, int64_t B, int64_t m, int64_
         e = hipGetLastError();
         if (e == hipSuccess) e = hipStreamSynchronize(o->loop.stream);  // the slab is overwritten next
     }
-    (void)hipFree(d_slab);
+    slab.release_all();
     if (e != hipSuccess) return bail(fail(ELLHIP_E_HIP, "batched svm table upload", e));
     *out = o;
     return 0;
@@ -154,9 +155,6 @@ void ellhip_batch_svm_destroy(ellhip_batch_svm* o) {
     if (!o) return;
     DeviceGuard guard(o->loop.device);
     batch_loop_free(o->loop);
-    void* bufs[] = {o->d_XT, o->d_labels, o->d_minidx, o->d_minval, o->d_x, o->d_grad, o->d_beta, o->d_margins};
-    for (void* p : bufs)
-        if (p) (void)hipFree(p);
     delete o;
 }
 

@@ -30,6 +30,7 @@
 #include "ellstable_kernels.hpp"
 #include "resident_kernels.hpp"
 #include "group_kernels.hpp"
+#include "device_allocs.hpp"
 
 using namespace ellhip;
 
@@ -69,28 +70,34 @@ struct ProfEvent {
     int cls;
 };
 
-// What a NEW handle starts with (ellhip_set_default_option; process-wide, not thread-safe by contract).  The values are
-// the measured best on MI355X; nothing here is read from the environment.
-struct Defaults {
-    int auto_defer = 1;        // ELLHIP_OPT_AUTO_DEFER
-    int symv = 1;              // ELLHIP_OPT_SYMV
-    long long symv_min_n = 5120;  // ELLHIP_OPT_SYMV_MIN_N
-    int apply_lower = 1;       // ELLHIP_OPT_APPLY_LOWER
-    int apply_kernel = -1;     // ELLHIP_OPT_APPLY_KERNEL (-1: by depth)
-    int fuse_dots = 1;         // ELLHIP_OPT_FUSE_DOTS
-    int resident = 1;          // ELLHIP_OPT_RESIDENT
-    int overlap = 1;           // ELLHIP_OPT_OVERLAP
-    int lookahead = 32;        // ELLHIP_OPT_LOOKAHEAD
-    int queue_depth = 48;      // ELLHIP_OPT_QUEUE_DEPTH
-    int apply_symm = 1;        // ELLHIP_OPT_APPLY_SYMM
-    int packed_operands = 1;   // ELLHIP_OPT_PACKED_OPERANDS
-    int stable_solve = 3;      // ELLHIP_OPT_STABLE_SOLVE
-    int stable_factor = 2;     // ELLHIP_OPT_STABLE_FACTOR
-    int pad = -1;              // ELLHIP_OPT_PAD: extra doubles per row of Q; -1 = by size (create_impl)
-    int lp_grid = 0;           // ELLHIP_OPT_LP_GRID: workgroups per LowpassOracle scan launch; 0 = by size
-    int lp_wide = -1;          // ELLHIP_OPT_LP_WIDE: column-split scan kernel; -1 = by size
-    int batch_threads = 0;     // ELLHIP_OPT_BATCH_THREADS: threads per workgroup of the batched engine; 0 = by size
-    int stage_direct = 1;      // ELLHIP_OPT_STAGE_DIRECT: on large-BAR systems the host writes gradients straight into device memory
+// The per-handle options (ellhip_set_option / ellhip_get_option) with their factory values: the measured best on MI355X;
+// nothing here is read from the environment.  Every handle carries one (ellhip_space derives from it), g_defaults holds
+// what a NEW handle starts with.  A new option is a field here and a row in g_option_table, nothing else.
+struct SpaceOptions {
+    long long symv = 1;              // ELLHIP_OPT_SYMV: allow the lower-triangle GEMV in deferred mode
+    long long symv_min_n = 5120;     // ELLHIP_OPT_SYMV_MIN_N: below this the full-row pass wins for synchronous updates (tools/midsize_sweep.py)
+    long long apply_lower = 1;       // ELLHIP_OPT_APPLY_LOWER: with symv: apply passes touch the lower triangle only
+    long long apply_kernel = -1;     // ELLHIP_OPT_APPLY_KERNEL: lower-triangle apply pass: 2 = k_apply_mfma, 1 = k_apply_lower, 0 = k_sweep_apply<LOWER> (depth 8); -1 = 2 at depth 24, else 1
+    long long fuse_dots = 1;         // ELLHIP_OPT_FUSE_DOTS: unsharded lower-triangle schedule: k_symv_reduce also yields the scalar stage's dot products
+    long long resident = 1;          // ELLHIP_OPT_RESIDENT: queue runs with the matrix parked on-chip (resident_kernels.hpp)
+    long long overlap = 1;           // ELLHIP_OPT_OVERLAP: the next cut's GEMV / the next group's products on a second stream
+    long long lookahead = 32;        // ELLHIP_OPT_LOOKAHEAD: GEMVs of up to this many consecutive queued cuts in ONE pass over Q_base
+    long long queue_depth = 48;      // ELLHIP_OPT_QUEUE_DEPTH: recorded updates a queue run on the group stage lets pile up before an apply pass (0: the handle's depth)
+    long long apply_symm = 1;        // ELLHIP_OPT_APPLY_SYMM: that apply pass rides on the next group's product pass (k_apply_symm_q; queue_run_multi)
+    long long packed_operands = 1;   // ELLHIP_OPT_PACKED_OPERANDS: the matrix-core passes fetch gradients and recorded vectors, and store column sums,
+                                     // 16 bytes per lane (k_pack_operands: gP in d_gT, colpart2 in d_colpart_m; unsharded handles)
+    long long stable_solve = 3;      // ELLHIP_OPT_STABLE_SOLVE: 0: one launch per block; 1: persistent solves; 2: persistent + helper workgroups; 3: 2 on the mirrored layout
+    long long stable_factor = 2;     // ELLHIP_OPT_STABLE_FACTOR: 0: tile kernel that reads the scratch triangle; 1: row kernel from U alone, beside the
+                                     // backward solve; 2: factor tiles pulled inside the helped backward solve's launch
+};
+// ... plus the values that exist as defaults only (ellhip_set_default_option; process-wide, not thread-safe by contract)
+struct Defaults : SpaceOptions {
+    long long auto_defer = 1;        // ELLHIP_OPT_AUTO_DEFER
+    long long pad = -1;              // ELLHIP_OPT_PAD: extra doubles per row of Q; -1 = by size (create_impl)
+    long long lp_grid = 0;           // ELLHIP_OPT_LP_GRID: workgroups per LowpassOracle scan launch; 0 = by size
+    long long lp_wide = -1;          // ELLHIP_OPT_LP_WIDE: column-split scan kernel; -1 = by size
+    long long batch_threads = 0;     // ELLHIP_OPT_BATCH_THREADS: threads per workgroup of the batched engine; 0 = by size
+    long long stage_direct = 1;      // ELLHIP_OPT_STAGE_DIRECT: on large-BAR systems the host writes gradients straight into device memory
 };
 Defaults g_defaults;
 
@@ -102,7 +109,8 @@ struct Shape {
 
 }  // namespace
 
-struct ellhip_space {
+struct ellhip_space : SpaceOptions {
+    Allocs mem;                      // owner of every d_* / h_* buffer below that is not an alias (device_allocs.hpp)
     int variant = ELLHIP_SPACE_ELL;
     long long n = 0, ld = 0, row0 = 0, nrows = 0;
     int device = 0;
@@ -116,10 +124,6 @@ struct ellhip_space {
     double* d_gt[2] = {nullptr, nullptr};      // buffers in use (own or caller's)
     double* d_work = nullptr;        // EllStable vectors: w, z, gg, q, beta2
     double* d_hpart = nullptr;       // EllStable forward solve with helper workgroups: the helpers' hand-over buffer (n)
-    // EllStable kernel forms (ellhip_set_option: ELLHIP_OPT_STABLE_SOLVE / ELLHIP_OPT_STABLE_FACTOR)
-    int stable_solve = 3;            // 0: one launch per block; 1: persistent solves; 2: persistent + helper workgroups; 3: 2 on the mirrored layout
-    int stable_factor = 2;           // 0: tile kernel that reads the scratch triangle; 1: row kernel from U alone, beside the
-                                     // backward solve; 2: factor tiles pulled inside the helped backward solve's launch
     int* d_fnext = nullptr;          // queue position of the factor tiles (reset by k_st_post before every launch)
     int* d_ftiles16 = nullptr;       // k_st_bwd_factor_helped: 16-row tiles (row group << 4 | segment)
     int nftiles16 = 0;
@@ -141,21 +145,15 @@ struct ellhip_space {
     double* d_colpart = nullptr;     // symmetric GEMV: per-strip column partial sums [n/SYMV_H][n]
     // pipelined queue runs on the lower-triangle schedule (ELLHIP_OPT_OVERLAP): the next cut's GEMV is issued on a second
     // stream beside this cut's reduction + scalar stage, into the other of two sets of partial sums
-    int overlap = 1;
     double* d_rowpart2 = nullptr;
     double* d_colpart2 = nullptr;
     int part_set = 0;                // the set the primed gradient's GEMV wrote / writes (see rowpart_of)
     hipStream_t symv_stream = nullptr;
     // ... and with the GEMVs of up to `lookahead` consecutive queued cuts computed in ONE pass over Q_base (k_symv_multi,
     // ELLHIP_OPT_LOOKAHEAD): vector l of a group writes partial-sum set 2 + l (slices of one allocation)
-    int lookahead = 32;
-    int queue_depth = 48;            // recorded updates a queue run on the group stage lets pile up before an apply pass (0: the handle's depth)
-    int apply_symm = 1;              // that apply pass rides on the next group's product pass (k_apply_symm_q; queue_run_multi)
     double* d_rowpart_m = nullptr;   // [MULTI_MAX][nsegs][n]
     double* d_colpart_m = nullptr;   // [MULTI_MAX][nstrips][n]
     double* d_gT = nullptr;          // [n][16]: a group's gradients side by side (operand layout of k_symm_mfma)
-    int packed_operands = 1;         // the matrix-core passes fetch gradients and recorded vectors, and store column sums, 16 bytes per lane
-                                     // (k_pack_operands: gP in d_gT, colpart2 in d_colpart_m; unsharded handles)
     double* d_pendP = nullptr;       // [n / 16][KS / 2][64][2]: the recorded vectors in the fused pass' operand order (MAXPEND n doubles)
     SymmTile* d_symm_tiles = nullptr;  // k_symm_mfma_q's tiles, largest first
     unsigned* d_symm_queue = nullptr;  // its two counters (one per half of the partial-sum sets), 128 bytes apart
@@ -173,27 +171,21 @@ struct ellhip_space {
     hipEvent_t ev_symv = nullptr;    // side_mark: what was issued on the second stream has finished
     hipEvent_t ev_side_go = nullptr; // side_fork: everything enqueued on the handle's stream up to the fork
     bool side_busy = false;          // work issued on the second stream has not been joined yet (side_fork .. side_join)
-    int symv = 1;                    // allow the lower-triangle GEMV in deferred mode (ELLHIP_SYMV=0 disables)
     int symv_rw = 2;
-    long long symv_min_n = 5120;     // below this the full-row pass wins for synchronous updates (tools/midsize_sweep.py)
     bool shard_symmetric = false;    // row shard whose GEMVs are partial symmetric sums (ellhip_set_shard_symmetric)
     int symv_seg = SYMV_SEG;         // segment width of the lower-triangle GEMV's tiles (see symv_alloc)
-    int apply_lower = 1;             // with symv: apply passes touch the lower triangle only (ELLHIP_APPLY_LOWER)
-    int fuse_dots = 1;               // unsharded lower-triangle schedule: k_symv_reduce also yields the scalar stage's dot products (ELLHIP_FUSE_DOTS)
     // queue runs with the matrix parked on-chip (resident_kernels.hpp, ELLHIP_OPT_RESIDENT)
-    int resident = 1;
     int rs_R = 0, rs_S = 0;          // super-tile edge / rows chosen for this n and device (0: does not fit)
     double* d_rs_part = nullptr;     // [2][grid][2 R 64]
     double* d_rs_omega = nullptr;    // [2][grid]
     unsigned* d_rs_bar = nullptr;    // RS_BAR_WORDS
     double* d_rs_xc0 = nullptr;      // xc at the start of the batch in flight (restored when the batch is abandoned)
     DevState* d_rs_st0 = nullptr;    // ... and the scalar state
-    long long rs_fault_at = -1;      // ELLHIP_OPT_RESIDENT_FAULT (test hook)
+    long long rs_fault_at = -1;      // ELLHIP_OPT_RESIDENT_FAULT (test hook; deliberately outside SpaceOptions: a clone does not inherit it)
     long long rs_abandoned = 0;      // batches abandoned and rerun on the streamed schedule (ELLHIP_OPT_RESIDENT_ABANDONED)
     int dots_np = 0;                 // > 0: d_partial holds dot products of the primed gradient for this depth: [ceil(n/128)][dots_np + 1]
                                      // from k_symv_reduce, or [scalar_groups(n)][...] WITHOUT the g.y column from k_sweep_gemv_dots
     bool dots_need_gy = false;       // the latter: k_scalar_apply_def forms g.y itself
-    int apply_kernel = -1;           // lower-triangle apply pass: 2 = k_apply_mfma, 1 = k_apply_lower, 0 = k_sweep_apply<LOWER> (depth 8); -1 = 2 at depth 24, else 1
     bool upper_stale = false;        // strict upper triangle of Q is out of date (see flush_pending)
     int defer = 1;                   // 1 = shrink Q at every cut; MAXPEND = record and apply in batches
     int npend = 0;                   // updates recorded since the last flush (host view, optimistic in queue mode)
@@ -335,19 +327,7 @@ void pick_shape(ellhip_space* s) {
         s->sh_fused = {2, 8, 1};
     }
     s->sh_apply = {4, 1, s->sh_fused.nt};  // 8 pending vectors per column step: more rows per workgroup amortise them
-    s->symv = g_defaults.symv;
-    s->symv_min_n = g_defaults.symv_min_n;
-    s->apply_lower = g_defaults.apply_lower;
-    s->apply_kernel = g_defaults.apply_kernel;
-    s->fuse_dots = g_defaults.fuse_dots;
-    s->overlap = g_defaults.overlap;
-    s->lookahead = g_defaults.lookahead;
-    s->queue_depth = g_defaults.queue_depth;
-    s->apply_symm = g_defaults.apply_symm;
-    s->packed_operands = g_defaults.packed_operands;
-    s->resident = g_defaults.resident;
-    s->stable_solve = g_defaults.stable_solve;
-    s->stable_factor = g_defaults.stable_factor;
+    static_cast<SpaceOptions&>(*s) = g_defaults;  // (what a new handle starts with)
 }
 
 // One pass over Q in the given roles.  gt_r1: vector of the rank-1 role; gvec / gv_out: operand and
@@ -770,22 +750,33 @@ bool symv_ok(const ellhip_space* s) {
     return s->sharded ? s->shard_symmetric : s->n >= s->symv_min_n;
 }
 
+// One set of partial sums of the lower-triangle GEMV, zeroed on the handle's stream: both buffers or neither
+// (rows of rowpart outside a shard are never written but are read by nobody either; they are zeroed anyway)
+int part_pair_alloc(ellhip_space* s, double*& rowpart, double*& colpart, size_t rbytes, size_t cbytes) {
+    const size_t mark = s->mem.mark();
+    hipError_t e = s->mem.device(rowpart, rbytes);
+    if (e == hipSuccess) e = s->mem.device(colpart, cbytes);
+    if (e == hipSuccess) e = hipMemsetAsync(rowpart, 0, rbytes, s->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(colpart, 0, cbytes, s->stream);
+    if (e == hipSuccess) return 0;
+    s->mem.rollback(mark);
+    return fail(ELLHIP_E_HIP, "partial-sum set of the lower-triangle GEMV", e);
+}
+
 int symv_alloc(ellhip_space* s) {
     if (s->d_rowpart || (s->n % 2) != 0 || s->n < 512 || (s->sharded && !s->shard_symmetric)) return 0;
     // tiles of 64 x 2048 in this handle's lower trapezoid; with fewer than ~200 (less than one per CU) the narrow
     // segments win (measured per rank at n = 16384: P = 8, 128 tiles: 0.049 vs 0.061 ms; P = 4, 256 tiles: 0.078 vs
     // 0.067; P = 2: 0.109 vs 0.104; unsharded n = 8192, 256 tiles: 0.076 vs 0.066)
     const double area = ((double)(s->row0 + s->nrows) * (double)(s->row0 + s->nrows) - (double)s->row0 * (double)s->row0) / 2.0;
-    s->symv_seg = (area / (64.0 * SYMV_SEG) < 200.0) ? SYMV_SEG_SMALL : SYMV_SEG;
+    const int seg = (area / (64.0 * SYMV_SEG) < 200.0) ? SYMV_SEG_SMALL : SYMV_SEG;
+    const size_t nsegs = (size_t)((s->n + seg - 1) / seg), nstrips = (size_t)((s->nrows + SYMV_H - 1) / SYMV_H);
+    const int rc = part_pair_alloc(s, s->d_rowpart, s->d_colpart, nsegs * (size_t)s->n * sizeof(double), nstrips * (size_t)s->n * sizeof(double));
+    if (rc) return rc;
+    s->symv_seg = seg;
     // rows in flight per thread: with about one 64 x 2048 tile per CU (n = 8192: 256 tiles) the workgroup itself has to
     // keep more loads in the air -- 4 rows: 61 vs 65 us per pass; with several tiles per CU (n = 16384) 2 and 4 tie
     s->symv_rw = (area / (64.0 * SYMV_SEG) < 600.0) ? 4 : 2;
-    const size_t nsegs = (size_t)((s->n + s->symv_seg - 1) / s->symv_seg), nstrips = (size_t)((s->nrows + SYMV_H - 1) / SYMV_H);
-    HIPCHK(hipMalloc(&s->d_rowpart, nsegs * (size_t)s->n * sizeof(double)));
-    HIPCHK(hipMalloc(&s->d_colpart, nstrips * (size_t)s->n * sizeof(double)));
-    // rows of rowpart outside this shard are never written but are read by nobody either; zero them anyway
-    HIPCHK(hipMemsetAsync(s->d_rowpart, 0, nsegs * (size_t)s->n * sizeof(double), s->stream));
-    HIPCHK(hipMemsetAsync(s->d_colpart, 0, nstrips * (size_t)s->n * sizeof(double), s->stream));
     return 0;
 }
 
@@ -1144,8 +1135,8 @@ int alloc_common(ellhip_space* s) {
     const size_t vbytes = (size_t)n * sizeof(double);
     HIPCHK(hipStreamCreateWithFlags(&s->own_stream, hipStreamNonBlocking));
     s->stream = s->own_stream;
-    HIPCHK(hipMalloc(&s->d_Q, (size_t)s->nrows * (size_t)s->ld * sizeof(double)));
-    HIPCHK(hipMalloc(&s->d_xc, vbytes));
+    HIPCHK(s->mem.device(s->d_Q, (size_t)s->nrows * (size_t)s->ld * sizeof(double)));
+    HIPCHK(s->mem.device(s->d_xc, vbytes));
     {   // Large-BAR systems: the host writes a gradient straight into device memory (fine-grained allocation: 3 us for 128 KiB)
         // instead of into a pinned buffer that a kernel then pulls over PCIe (0.8 + 7.6 us and a launch on the live loop's
         // critical path, tools/experiments/bar_write.hip).
@@ -1155,39 +1146,35 @@ int alloc_common(ellhip_space* s) {
         s->stage_direct = large_bar != 0 && g_defaults.stage_direct != 0;
     }
     if (s->stage_direct) {
+        const size_t mark = s->mem.mark();
         for (int k = 0; k < 2 && s->stage_direct; ++k)
-            if (hipExtMallocWithFlags(reinterpret_cast<void**>(&s->d_stage[k]), vbytes, hipDeviceMallocFinegrained) != hipSuccess) {
+            if (s->mem.device_finegrained(s->d_stage[k], vbytes) != hipSuccess) {
                 (void)hipGetLastError();
-                s->d_stage[k] = nullptr;
+                s->mem.rollback(mark);
                 s->stage_direct = false;
-            }
-        if (!s->stage_direct)
-            for (int k = 0; k < 2; ++k) {
-                if (s->d_stage[k]) (void)hipFree(s->d_stage[k]);
-                s->d_stage[k] = nullptr;
             }
     }
     if (!s->stage_direct)
-        for (int k = 0; k < 2; ++k) HIPCHK(hipMalloc(&s->d_stage[k], vbytes));
+        for (int k = 0; k < 2; ++k) HIPCHK(s->mem.device(s->d_stage[k], vbytes));
     for (int k = 0; k < 2; ++k) {
-        HIPCHK(hipMalloc(&s->d_gt_own[k], vbytes));
+        HIPCHK(s->mem.device(s->d_gt_own[k], vbytes));
         s->d_gt[k] = s->d_gt_own[k];
-        HIPCHK(hipHostMalloc(&s->h_stage[k], vbytes, hipHostMallocCoherent | hipHostMallocMapped));  // (k_stage reads it from the device)
+        HIPCHK(s->mem.pinned(s->h_stage[k], vbytes, hipHostMallocCoherent | hipHostMallocMapped));  // (k_stage reads it from the device)
         HIPCHK(hipMemsetAsync(s->d_gt_own[k], 0, vbytes, s->stream));
     }
-    HIPCHK(hipMalloc(&s->d_st, sizeof(DevState)));
+    HIPCHK(s->mem.device(s->d_st, sizeof(DevState)));
     // partial sums of the scalar stage: [scalar_groups(n) <= 64][MAXPEND + 1], or [ceil(n / 128)][depth + 1] when the
     // lower-triangle GEMV's reduction produces them
-    HIPCHK(hipMalloc(&s->d_partial, (size_t)std::max<long long>(64, (n + 127) / 128) * (MAXPEND + 1) * sizeof(double)));
+    HIPCHK(s->mem.device(s->d_partial, (size_t)std::max<long long>(64, (n + 127) / 128) * (MAXPEND + 1) * sizeof(double)));
     if (s->variant == ELLHIP_SPACE_ELL) {
-        HIPCHK(hipMalloc(&s->d_pend, (size_t)MAXPEND * vbytes));
-        HIPCHK(hipMalloc(&s->d_cpend, MAXPEND * sizeof(double)));
+        HIPCHK(s->mem.device(s->d_pend, (size_t)MAXPEND * vbytes));
+        HIPCHK(s->mem.device(s->d_cpend, MAXPEND * sizeof(double)));
         HIPCHK(hipMemsetAsync(s->d_pend, 0, (size_t)MAXPEND * vbytes, s->stream));
         HIPCHK(hipMemsetAsync(s->d_cpend, 0, MAXPEND * sizeof(double), s->stream));
     }
     if (s->variant == ELLHIP_SPACE_ELL_STABLE) {
         const size_t nflags = (size_t)std::max<long long>(512, (n + SB - 1) / SB);
-        HIPCHK(hipMalloc(&s->d_flags, nflags * sizeof(int)));
+        HIPCHK(s->mem.device(s->d_flags, nflags * sizeof(int)));
         HIPCHK(hipMemsetAsync(s->d_flags, 0, nflags * sizeof(int), s->stream));
         {   // how many workgroups of each persistent solve this device keeps resident at once
             hipDeviceProp_t prop;
@@ -1216,13 +1203,13 @@ int alloc_common(ellhip_space* s) {
                 }
             f16.insert(f16.end(), e16.begin(), e16.end());
             s->nftiles16 = (int)f16.size();
-            HIPCHK(hipMalloc(&s->d_fnext, sizeof(int)));
+            HIPCHK(s->mem.device(s->d_fnext, sizeof(int)));
             HIPCHK(hipMemsetAsync(s->d_fnext, 0, sizeof(int), s->stream));
             if (s->nftiles16 > 0) {
-                HIPCHK(hipMalloc(&s->d_ftiles16, f16.size() * sizeof(int)));
+                HIPCHK(s->mem.device(s->d_ftiles16, f16.size() * sizeof(int)));
                 HIPCHK(hipMemcpyAsync(s->d_ftiles16, f16.data(), f16.size() * sizeof(int), hipMemcpyHostToDevice, s->stream));
                 HIPCHK(hipStreamSynchronize(s->stream));  // `f16` goes out of scope
-                HIPCHK(hipMalloc(&s->d_qhpart, vbytes));
+                HIPCHK(s->mem.device(s->d_qhpart, vbytes));
                 hipLaunchKernelGGL(k_st_arm, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s->stream, s->d_qhpart, n);
             }
         }
@@ -1231,23 +1218,23 @@ int alloc_common(ellhip_space* s) {
         HIPCHK(hipEventCreateWithFlags(&s->ev_join, hipEventDisableTiming));
     }
     if (s->variant == ELLHIP_SPACE_ELL_STABLE) {
-        HIPCHK(hipMalloc(&s->d_work, vbytes * 8 + (ST_MID_T + 8) * sizeof(double)));  // w0 z gg q beta2 qpub w1 (+1 spare) | cpre
+        HIPCHK(s->mem.device(s->d_work, vbytes * 8 + (ST_MID_T + 8) * sizeof(double)));  // w0 z gg q beta2 qpub w1 (+1 spare) | cpre
         // both publish buffers of the persistent forward solve start out all-sentinel
         hipLaunchKernelGGL(k_st_arm, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s->stream, s->d_work, n);
         hipLaunchKernelGGL(k_st_arm, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s->stream, s->d_work + 6 * n, n);
-        HIPCHK(hipMalloc(&s->d_hpart, vbytes));
+        HIPCHK(s->mem.device(s->d_hpart, vbytes));
         hipLaunchKernelGGL(k_st_arm, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s->stream, s->d_hpart, n);
-        HIPCHK(hipMalloc(&s->d_stpend, sizeof(StPend)));
-        HIPCHK(hipMalloc(&s->d_rbuf, 2 * vbytes));
-        HIPCHK(hipMalloc(&s->d_wkeep, vbytes));
+        HIPCHK(s->mem.device(s->d_stpend, sizeof(StPend)));
+        HIPCHK(s->mem.device(s->d_rbuf, 2 * vbytes));
+        HIPCHK(s->mem.device(s->d_wkeep, vbytes));
         hipLaunchKernelGGL(k_st_mirror_clear, dim3(1), dim3(1), 0, s->stream, s->d_stpend);
         HIPCHK(hipGetLastError());
     }
-    HIPCHK(hipHostMalloc(&s->h_result, sizeof(DevState), hipHostMallocDefault));
-    HIPCHK(hipHostMalloc(&s->h_live, sizeof(LiveMirror), hipHostMallocCoherent | hipHostMallocMapped));
-    HIPCHK(hipHostMalloc(&s->h_xc, vbytes, hipHostMallocCoherent | hipHostMallocMapped));
+    HIPCHK(s->mem.pinned(s->h_result, sizeof(DevState), hipHostMallocDefault));
+    HIPCHK(s->mem.pinned(s->h_live, sizeof(LiveMirror), hipHostMallocCoherent | hipHostMallocMapped));
+    HIPCHK(s->mem.pinned(s->h_xc, vbytes, hipHostMallocCoherent | hipHostMallocMapped));
     memset(s->h_live, 0, sizeof(LiveMirror));
-    HIPCHK(hipMalloc(&s->d_pub_arrived, sizeof(unsigned)));
+    HIPCHK(s->mem.device(s->d_pub_arrived, sizeof(unsigned)));
     HIPCHK(hipMemsetAsync(s->d_pub_arrived, 0, sizeof(unsigned), s->stream));
     return 0;
 }
@@ -1385,14 +1372,10 @@ int create_impl(ellhip_space** out, int variant, long long n, long long row0, lo
 }
 
 void queue_free(ellhip_space* s) {
-    if (s->d_qparams) (void)hipFree(s->d_qparams);
-    if (s->d_qgrads) (void)hipFree(s->d_qgrads);
-    if (s->d_qstatus) (void)hipFree(s->d_qstatus);
-    if (s->d_qtsq) (void)hipFree(s->d_qtsq);
-    s->d_qparams = nullptr;
-    s->d_qgrads = nullptr;
-    s->d_qstatus = nullptr;
-    s->d_qtsq = nullptr;
+    s->mem.free(s->d_qparams);
+    s->mem.free(s->d_qgrads);
+    s->mem.free(s->d_qstatus);
+    s->mem.free(s->d_qtsq);
     s->qk = 0;
 }
 
@@ -1475,12 +1458,17 @@ bool overlap_ok(const ellhip_space* s) {
 int side_setup(ellhip_space* s) {
     if (s->symv_stream) return 0;
     int least = 0, greatest = 0;
-    HIPCHK(hipDeviceGetStreamPriorityRange(&least, &greatest));
-    HIPCHK(hipEventCreateWithFlags(&s->ev_symv, hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&s->ev_side_go, hipEventDisableTiming));
+    hipError_t e = hipDeviceGetStreamPriorityRange(&least, &greatest);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&s->ev_symv, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&s->ev_side_go, hipEventDisableTiming);
     // lowest priority: the short reduction / scalar kernels of the main stream get the CU slots the GEMV's workgroups free
-    HIPCHK(hipStreamCreateWithPriority(&s->symv_stream, hipStreamNonBlocking, least));
-    return 0;
+    if (e == hipSuccess) e = hipStreamCreateWithPriority(&s->symv_stream, hipStreamNonBlocking, least);
+    if (e == hipSuccess) return 0;
+    if (s->ev_symv) (void)hipEventDestroy(s->ev_symv);  // all three or none (the stream, created last, is the mark)
+    if (s->ev_side_go) (void)hipEventDestroy(s->ev_side_go);
+    s->ev_symv = s->ev_side_go = nullptr;
+    s->symv_stream = nullptr;
+    return fail(ELLHIP_E_HIP, "second stream of the queue runs", e);
 }
 hipStream_t side_stream(const ellhip_space* s) { return s->overlap == 2 ? s->stream : s->symv_stream; }
 int side_join(ellhip_space* s) {
@@ -1512,12 +1500,7 @@ int overlap_setup(ellhip_space* s) {
     if (s->d_rowpart2) return 0;
     int rc = side_setup(s);
     if (rc) return rc;
-    const size_t nsegs = (size_t)((s->n + s->symv_seg - 1) / s->symv_seg), nstrips = (size_t)((s->nrows + SYMV_H - 1) / SYMV_H);
-    HIPCHK(hipMalloc(&s->d_rowpart2, nsegs * (size_t)s->n * sizeof(double)));
-    HIPCHK(hipMalloc(&s->d_colpart2, nstrips * (size_t)s->n * sizeof(double)));
-    HIPCHK(hipMemsetAsync(s->d_rowpart2, 0, nsegs * (size_t)s->n * sizeof(double), s->stream));
-    HIPCHK(hipMemsetAsync(s->d_colpart2, 0, nstrips * (size_t)s->n * sizeof(double), s->stream));
-    return 0;
+    return part_pair_alloc(s, s->d_rowpart2, s->d_colpart2, rowpart_elems(s) * sizeof(double), colpart_elems(s) * sizeof(double));
 }
 
 int queue_run_overlapped(ellhip_space* s, long long first, long long count) {
@@ -1586,24 +1569,10 @@ bool multi_shard_ok(const ellhip_space* s) {
 
 constexpr int MULTI_NO_MEMORY = 1;  // multi_setup: the buffers do not fit; the handle has been switched to lookahead 1
 
-void multi_free(ellhip_space* s) {
-    double** bufs[] = {&s->d_rowpart_m, &s->d_colpart_m, &s->d_gT, &s->d_pendP, &s->d_grpY, &s->d_gpart, &s->d_cpart, &s->d_gsums};
-    for (double** b : bufs) {
-        if (*b) (void)hipFree(*b);
-        *b = nullptr;
-    }
-    if (s->d_gout) (void)hipFree(s->d_gout);
-    s->d_gout = nullptr;
-    if (s->d_symm_tiles) (void)hipFree(s->d_symm_tiles);
-    s->d_symm_tiles = nullptr;
-    if (s->d_symm_queue) (void)hipFree(s->d_symm_queue);
-    s->d_symm_queue = nullptr;
-    s->symm_ntiles = 0;
-}
-
 // The group runs' buffers: 2 x 32 sets of partial sums (n^2 / 64 + n^2 / 2048 doubles each) are about n^2 doubles beside
 // the matrix' n^2 (4.4 GB at n = 32768).  When they do not fit, the handle continues with one product per pass
 // (returns MULTI_NO_MEMORY once; ELLHIP_OPT_LOOKAHEAD reads 1 afterwards): slower, not an error.
+int multi_fill(ellhip_space* s, const std::vector<SymmTile>& tiles);
 int multi_setup(ellhip_space* s) {
     if (s->d_rowpart_m) return 0;
     const size_t nb = (size_t)((s->n + 127) / 128);
@@ -1611,15 +1580,16 @@ int multi_setup(ellhip_space* s) {
     // stream while this group's stage reads the other half
     const size_t rbytes = (size_t)2 * MULTI_MAX * rowpart_elems(s) * sizeof(double);
     const size_t cbytes = (size_t)2 * MULTI_MAX * colpart_elems(s) * sizeof(double);
-    hipError_t e = hipMalloc(&s->d_rowpart_m, rbytes);
-    if (e == hipSuccess) e = hipMalloc(&s->d_colpart_m, cbytes);
-    if (e == hipSuccess) e = hipMalloc(&s->d_gT, (size_t)2 * s->n * MULTI_MAX * sizeof(double));
-    if (e == hipSuccess && !s->sharded) e = hipMalloc(&s->d_pendP, (size_t)MAXPEND * (size_t)s->n * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc(&s->d_grpY, (size_t)GRP_MAX * (size_t)s->n * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc(&s->d_gpart, (size_t)GRP_MAX * nb * (MAXPEND + 1) * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc(&s->d_cpart, nb * GRP_MAX * GRP_MAX * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc(&s->d_gout, sizeof(GroupOut));
-    if (e == hipSuccess) e = hipMalloc(&s->d_gsums, (size_t)(GRP_MAX * (MAXPEND + 1) + GRP_MAX * GRP_MAX) * sizeof(double));
+    const size_t mark = s->mem.mark();
+    hipError_t e = s->mem.device(s->d_rowpart_m, rbytes);
+    if (e == hipSuccess) e = s->mem.device(s->d_colpart_m, cbytes);
+    if (e == hipSuccess) e = s->mem.device(s->d_gT, (size_t)2 * s->n * MULTI_MAX * sizeof(double));
+    if (e == hipSuccess && !s->sharded) e = s->mem.device(s->d_pendP, (size_t)MAXPEND * (size_t)s->n * sizeof(double));
+    if (e == hipSuccess) e = s->mem.device(s->d_grpY, (size_t)GRP_MAX * (size_t)s->n * sizeof(double));
+    if (e == hipSuccess) e = s->mem.device(s->d_gpart, (size_t)GRP_MAX * nb * (MAXPEND + 1) * sizeof(double));
+    if (e == hipSuccess) e = s->mem.device(s->d_cpart, nb * GRP_MAX * GRP_MAX * sizeof(double));
+    if (e == hipSuccess) e = s->mem.device(s->d_gout, sizeof(GroupOut));
+    if (e == hipSuccess) e = s->mem.device(s->d_gsums, (size_t)(GRP_MAX * (MAXPEND + 1) + GRP_MAX * GRP_MAX) * sizeof(double));
     // the matrix-core pass draws its tiles from a queue, largest first (k_symm_mfma_q)
     std::vector<SymmTile> tiles;
     if ((s->n % 64) == 0 && (s->row0 % 64) == 0) {  // (whatever the lookahead is right now: the option may change)
@@ -1633,19 +1603,28 @@ int multi_setup(ellhip_space* s) {
             for (long long J = 0; J < nsegs; ++J)
                 if (J * seg <= s->row0 + I * SYMV_H + SYMV_H - 1) tiles.push_back({(int)I, (int)J});
         std::stable_sort(tiles.begin(), tiles.end(), [&](const SymmTile& a, const SymmTile& b) { return blocks_of(a) > blocks_of(b); });
-        if (e == hipSuccess) e = hipMalloc(&s->d_symm_tiles, tiles.size() * sizeof(SymmTile));
-        if (e == hipSuccess) e = hipMalloc(&s->d_symm_queue, 256);
+        if (e == hipSuccess) e = s->mem.device(s->d_symm_tiles, tiles.size() * sizeof(SymmTile));
+        if (e == hipSuccess) e = s->mem.device(s->d_symm_queue, 256);
     }
+    if (e != hipSuccess) s->mem.rollback(mark);
     if (e == hipErrorOutOfMemory) {
         (void)hipGetLastError();
-        multi_free(s);
         s->lookahead = 1;
         return MULTI_NO_MEMORY;
     }
-    if (e != hipSuccess) {
-        multi_free(s);
-        return fail(ELLHIP_E_HIP, "hipMalloc (group-run buffers)", e);
+    if (e != hipSuccess) return fail(ELLHIP_E_HIP, "buffers of the group runs", e);
+    const int rc = multi_fill(s, tiles);
+    if (rc) {  // all or nothing: d_rowpart_m, the "already set up" mark, only stays with everything behind it in place
+        s->mem.rollback(mark);
+        s->symm_ntiles = s->symm_wgs = 0;
     }
+    return rc;
+}
+
+// (multi_setup: what the buffers hold before their first use, the tile list, and one empty launch of each pass)
+int multi_fill(ellhip_space* s, const std::vector<SymmTile>& tiles) {
+    const size_t rbytes = (size_t)2 * MULTI_MAX * rowpart_elems(s) * sizeof(double);
+    const size_t cbytes = (size_t)2 * MULTI_MAX * colpart_elems(s) * sizeof(double);
     HIPCHK(hipMemsetAsync(s->d_rowpart_m, 0, rbytes, s->stream));
     HIPCHK(hipMemsetAsync(s->d_colpart_m, 0, cbytes, s->stream));
     HIPCHK(hipMemsetAsync(s->d_gout, 0, sizeof(GroupOut), s->stream));
@@ -1708,6 +1687,16 @@ int multi_setup(ellhip_space* s) {
         HIPCHK(hipGetLastError());
     }
     return 0;
+}
+
+// (give the group runs' buffers back: the ranks of a sharded handle agreed to run cut by cut, sharded_capi.inc.hpp)
+void multi_free(ellhip_space* s) {
+    double** bufs[] = {&s->d_rowpart_m, &s->d_colpart_m, &s->d_gT, &s->d_pendP, &s->d_grpY, &s->d_gpart, &s->d_cpart, &s->d_gsums};
+    for (double** b : bufs) s->mem.free(*b);
+    s->mem.free(s->d_gout);
+    s->mem.free(s->d_symm_tiles);
+    s->mem.free(s->d_symm_queue);
+    s->symm_ntiles = 0;
 }
 
 // ELLHIP_OPT_PACKED_OPERANDS: the passes of this handle's group runs take the packed forms (a queue run keeps one form from its
@@ -2072,10 +2061,12 @@ constexpr long long RS_MIN_COUNT = 4;
 
 int resident_setup(ellhip_space* s) {  // once per handle: can this n run resident on this device, and with which R?
     if (s->rs_R != 0) return 0;
-    s->rs_R = -1;
-    if (s->variant != ELLHIP_SPACE_ELL || s->sharded) return 0;
+    if (s->variant != ELLHIP_SPACE_ELL || s->sharded) {
+        s->rs_R = -1;
+        return 0;
+    }
     hipDeviceProp_t prop;
-    HIPCHK(hipGetDeviceProperties(&prop, s->device));
+    HIPCHK(hipGetDeviceProperties(&prop, s->device));  // (rs_R stays 0 on every failure: the next queue run asks again)
     const int T = (int)((s->n + RS_TS - 1) / RS_TS);
     for (int r = 1; r <= RS_RMAX; ++r) {
         const int S = (T + r - 1) / r;
@@ -2084,15 +2075,21 @@ int resident_setup(ellhip_space* s) {  // once per handle: can this n run reside
         const void* k = r == 1 ? (const void*)k_ell_resident<1> : (r == 2 ? (const void*)k_ell_resident<2> : (const void*)k_ell_resident<3>);
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k, RS_THREADS, 0) != hipSuccess || occ < 1) continue;
         const size_t G = (size_t)S * (S + 1) / 2, NV = 2 * (size_t)r * RS_TS;
-        HIPCHK(hipMalloc(&s->d_rs_part, 2 * G * NV * sizeof(double)));
-        HIPCHK(hipMalloc(&s->d_rs_omega, 2 * G * sizeof(double)));
-        HIPCHK(hipMalloc(&s->d_rs_bar, RS_BAR_WORDS * sizeof(unsigned)));
-        HIPCHK(hipMalloc(&s->d_rs_xc0, (size_t)s->n * sizeof(double)));
-        HIPCHK(hipMalloc(&s->d_rs_st0, sizeof(DevState)));
+        const size_t mark = s->mem.mark();
+        hipError_t e = s->mem.device(s->d_rs_part, 2 * G * NV * sizeof(double));
+        if (e == hipSuccess) e = s->mem.device(s->d_rs_omega, 2 * G * sizeof(double));
+        if (e == hipSuccess) e = s->mem.device(s->d_rs_bar, RS_BAR_WORDS * sizeof(unsigned));
+        if (e == hipSuccess) e = s->mem.device(s->d_rs_xc0, (size_t)s->n * sizeof(double));
+        if (e == hipSuccess) e = s->mem.device(s->d_rs_st0, sizeof(DevState));
+        if (e != hipSuccess) {
+            s->mem.rollback(mark);
+            return fail(ELLHIP_E_HIP, "buffers of the resident queue runs", e);
+        }
         s->rs_R = r;
         s->rs_S = S;
-        break;
+        return 0;
     }
+    s->rs_R = -1;  // does not fit this device
     return 0;
 }
 
@@ -2242,58 +2239,14 @@ void ellhip_destroy(ellhip_space* s) {
     if (s->stream) (void)hipStreamSynchronize(s->stream);
     if (s->aux_stream) (void)hipStreamSynchronize(s->aux_stream);  // nothing may be in flight when the buffers go
     if (s->symv_stream) (void)hipStreamSynchronize(s->symv_stream);
+    s->mem.release_all();  // (while the guard is alive, before the streams go)
     for (auto& pe : s->prof_events) {
         (void)hipEventDestroy(pe.a);
         (void)hipEventDestroy(pe.b);
     }
-    queue_free(s);
-    if (s->d_Q) (void)hipFree(s->d_Q);
-    if (s->d_xc) (void)hipFree(s->d_xc);
-    for (int k = 0; k < 2; ++k) {
-        if (s->d_stage[k]) (void)hipFree(s->d_stage[k]);
-        if (s->d_gt_own[k]) (void)hipFree(s->d_gt_own[k]);
-        if (s->h_stage[k]) (void)hipHostFree(s->h_stage[k]);
-    }
-    if (s->d_work) (void)hipFree(s->d_work);
-    if (s->d_hpart) (void)hipFree(s->d_hpart);
-    if (s->d_stpend) (void)hipFree(s->d_stpend);
-    if (s->d_rbuf) (void)hipFree(s->d_rbuf);
-    if (s->d_wkeep) (void)hipFree(s->d_wkeep);
-    if (s->d_fnext) (void)hipFree(s->d_fnext);
-    if (s->d_ftiles16) (void)hipFree(s->d_ftiles16);
-    if (s->d_qhpart) (void)hipFree(s->d_qhpart);
-    if (s->d_partial) (void)hipFree(s->d_partial);
-    if (s->d_pend) (void)hipFree(s->d_pend);
-    if (s->d_cpend) (void)hipFree(s->d_cpend);
-    if (s->d_rs_part) (void)hipFree(s->d_rs_part);
-    if (s->d_rs_omega) (void)hipFree(s->d_rs_omega);
-    if (s->d_rs_bar) (void)hipFree(s->d_rs_bar);
-    if (s->d_rs_xc0) (void)hipFree(s->d_rs_xc0);
-    if (s->d_rs_st0) (void)hipFree(s->d_rs_st0);
-    if (s->d_rowpart) (void)hipFree(s->d_rowpart);
-    if (s->d_colpart) (void)hipFree(s->d_colpart);
-    if (s->d_rowpart2) (void)hipFree(s->d_rowpart2);
-    if (s->d_colpart2) (void)hipFree(s->d_colpart2);
-    if (s->d_rowpart_m) (void)hipFree(s->d_rowpart_m);
-    if (s->d_colpart_m) (void)hipFree(s->d_colpart_m);
-    if (s->d_gT) (void)hipFree(s->d_gT);
-    if (s->d_pendP) (void)hipFree(s->d_pendP);
-    if (s->d_grpY) (void)hipFree(s->d_grpY);
-    if (s->d_gpart) (void)hipFree(s->d_gpart);
-    if (s->d_cpart) (void)hipFree(s->d_cpart);
-    if (s->d_gout) (void)hipFree(s->d_gout);
-    if (s->d_gsums) (void)hipFree(s->d_gsums);
-    if (s->d_symm_tiles) (void)hipFree(s->d_symm_tiles);
-    if (s->d_symm_queue) (void)hipFree(s->d_symm_queue);
     if (s->ev_symv) (void)hipEventDestroy(s->ev_symv);
     if (s->ev_side_go) (void)hipEventDestroy(s->ev_side_go);
     if (s->symv_stream) (void)hipStreamDestroy(s->symv_stream);
-    if (s->d_flags) (void)hipFree(s->d_flags);
-    if (s->d_st) (void)hipFree(s->d_st);
-    if (s->h_result) (void)hipHostFree(s->h_result);
-    if (s->h_live) (void)hipHostFree(s->h_live);
-    if (s->h_xc) (void)hipHostFree(s->h_xc);
-    if (s->d_pub_arrived) (void)hipFree(s->d_pub_arrived);
     if (s->ev_fork) (void)hipEventDestroy(s->ev_fork);
     if (s->ev_join) (void)hipEventDestroy(s->ev_join);
     if (s->aux_stream) (void)hipStreamDestroy(s->aux_stream);
@@ -2326,23 +2279,11 @@ int ellhip_clone(const ellhip_space* src_c, ellhip_space** out) {
     s->sh_rank1 = src->sh_rank1;
     s->sh_fused = src->sh_fused;
     s->sh_apply = src->sh_apply;
-    s->symv = src->symv;
+    static_cast<SpaceOptions&>(*s) = *src;  // every option; not rs_fault_at (the test hook stays with its handle)
     s->symv_rw = src->symv_rw;
-    s->symv_min_n = src->symv_min_n;
-    s->apply_lower = src->apply_lower;
-    s->apply_kernel = src->apply_kernel;
-    s->fuse_dots = src->fuse_dots;
-    s->overlap = src->overlap;
-    s->lookahead = src->lookahead;
-    s->queue_depth = src->queue_depth;
-    s->apply_symm = src->apply_symm;
-    s->packed_operands = src->packed_operands;
-    s->resident = src->resident;
     s->shard_symmetric = src->shard_symmetric;
     s->upper_stale = src->upper_stale;
     s->symv_seg = src->symv_seg;
-    s->stable_solve = src->stable_solve;
-    s->stable_factor = src->stable_factor;
     rc = alloc_common(s);
     if (rc) {
         ellhip_destroy(s);
@@ -2639,183 +2580,165 @@ int ellhip_set_shard_symmetric(ellhip_space* s, int flag) {
 }
 
 // ---- options ----------------------------------------------------------------------------------
+// One row per ELLHIP_OPT_* key: the four entry points below read nothing else.  A new option is a field of SpaceOptions
+// (or of Defaults, when it exists as a default only) and a row here.
 namespace {
-int option_ok(int key, long long v) {
-    switch (key) {
-        case ELLHIP_OPT_APPLY_KERNEL:
-            return (v >= -1 && v <= 2) ? 0 : fail(ELLHIP_E_INVALID, "option value must be -1, 0, 1 or 2");
-        case ELLHIP_OPT_STAGE_DIRECT: case ELLHIP_OPT_APPLY_SYMM: case ELLHIP_OPT_PACKED_OPERANDS:
-            return (v == 0 || v == 1) ? 0 : fail(ELLHIP_E_INVALID, "option value must be 0 or 1");
-        case ELLHIP_OPT_AUTO_DEFER: case ELLHIP_OPT_SYMV: case ELLHIP_OPT_APPLY_LOWER:
-        case ELLHIP_OPT_FUSE_DOTS:
-            return (v == 0 || v == 1) ? 0 : fail(ELLHIP_E_INVALID, "option value must be 0 or 1");
-        case ELLHIP_OPT_RESIDENT: return (v >= 0 && v <= 2) ? 0 : fail(ELLHIP_E_INVALID, "ELLHIP_OPT_RESIDENT: 0, 1 or 2");
-        case ELLHIP_OPT_OVERLAP: return (v >= 0 && v <= 2) ? 0 : fail(ELLHIP_E_INVALID, "ELLHIP_OPT_OVERLAP: 0, 1 or 2");
-        case ELLHIP_OPT_LOOKAHEAD: return (v >= 1 && v <= 32) ? 0 : fail(ELLHIP_E_INVALID, "ELLHIP_OPT_LOOKAHEAD: 1 .. 32");
-        case ELLHIP_OPT_QUEUE_DEPTH: return (v == 0 || v == 48) ? 0 : fail(ELLHIP_E_INVALID, "ELLHIP_OPT_QUEUE_DEPTH: 0 or 48");
-        case ELLHIP_OPT_RESIDENT_FAULT: return v >= -1 ? 0 : fail(ELLHIP_E_INVALID, "ELLHIP_OPT_RESIDENT_FAULT: -1 or a cut index");
-        case ELLHIP_OPT_SYMV_MIN_N: return v >= 512 ? 0 : fail(ELLHIP_E_INVALID, "ELLHIP_OPT_SYMV_MIN_N must be >= 512");
-        case ELLHIP_OPT_STABLE_SOLVE: return (v >= 0 && v <= 3) ? 0 : fail(ELLHIP_E_INVALID, "ELLHIP_OPT_STABLE_SOLVE: 0 .. 3");
-        case ELLHIP_OPT_STABLE_FACTOR:
-            return (v >= 0 && v <= 2) ? 0 : fail(ELLHIP_E_INVALID, "option value must be 0, 1 or 2");
-        case ELLHIP_OPT_PAD: return (v >= -1 && v <= 4096) ? 0 : fail(ELLHIP_E_INVALID, "ELLHIP_OPT_PAD: -1 .. 4096");
-        case ELLHIP_OPT_LP_GRID: return (v >= 0 && v <= 65536) ? 0 : fail(ELLHIP_E_INVALID, "ELLHIP_OPT_LP_GRID: 0 .. 65536");
-        case ELLHIP_OPT_LP_WIDE: return (v >= -1 && v <= 1) ? 0 : fail(ELLHIP_E_INVALID, "ELLHIP_OPT_LP_WIDE: -1, 0, 1");
-        case ELLHIP_OPT_BATCH_THREADS:
-            return (v == 0 || v == 64 || v == 128 || v == 256) ? 0 : fail(ELLHIP_E_INVALID, "ELLHIP_OPT_BATCH_THREADS: 0, 64, 128, 256");
-        default: return fail(ELLHIP_E_INVALID, "unknown option key");
+enum OptWho : unsigned char { OPT_DEFAULT_ONLY, OPT_ELL, OPT_STABLE, OPT_READ_ONLY };  // who may set it (on a handle: Ell / EllStable only)
+// what ellhip_set_option does first: nothing (read per queue run); make Q current (what has been recorded, and a stale upper
+// triangle, belong to the schedule in force); leave the mirrored layout (the next update enters the layout its options ask for)
+enum OptFirst : unsigned char { FIRST_NOTHING, FIRST_Q_CURRENT, FIRST_LEAVE_MIRROR };
+constexpr long long OPT_NO_MAX = 0x7fffffffffffffffLL;
+struct OptAllowed {  // a range lo .. hi (empty: nothing may be stored), or (nset > 0) a set
+    long long lo, hi;
+    int nset;
+    long long set[4];
+};
+constexpr OptAllowed range(long long lo, long long hi) { return {lo, hi, 0, {}}; }
+constexpr OptAllowed at_least(long long lo) { return {lo, OPT_NO_MAX, 0, {}}; }
+struct OptionRow {
+    int key;
+    const char* name;
+    long long SpaceOptions::*opt;  // where the value lives: a per-handle option (in every handle and in g_defaults),
+    long long* def_only;           // a default-only value (in g_defaults), or neither (per-handle state outside the record)
+    OptAllowed allowed;
+    OptWho who;
+    OptFirst first;
+};
+#define OPT_ROW(KEY, FIELD, ...) {ELLHIP_OPT_##KEY, "ELLHIP_OPT_" #KEY, &SpaceOptions::FIELD, nullptr, __VA_ARGS__}
+#define OPT_DEF(KEY, FIELD, ...) {ELLHIP_OPT_##KEY, "ELLHIP_OPT_" #KEY, nullptr, &g_defaults.FIELD, __VA_ARGS__, OPT_DEFAULT_ONLY, FIRST_NOTHING}
+#define OPT_OWN(KEY, ...) {ELLHIP_OPT_##KEY, "ELLHIP_OPT_" #KEY, nullptr, nullptr, __VA_ARGS__, FIRST_NOTHING}
+const OptionRow g_option_table[] = {
+    OPT_DEF(AUTO_DEFER, auto_defer, range(0, 1)),
+    OPT_ROW(SYMV, symv, range(0, 1), OPT_ELL, FIRST_Q_CURRENT),
+    OPT_ROW(SYMV_MIN_N, symv_min_n, at_least(512), OPT_ELL, FIRST_Q_CURRENT),
+    OPT_ROW(APPLY_LOWER, apply_lower, range(0, 1), OPT_ELL, FIRST_Q_CURRENT),
+    OPT_ROW(APPLY_KERNEL, apply_kernel, range(-1, 2), OPT_ELL, FIRST_Q_CURRENT),
+    OPT_ROW(FUSE_DOTS, fuse_dots, range(0, 1), OPT_ELL, FIRST_Q_CURRENT),
+    OPT_ROW(STABLE_SOLVE, stable_solve, range(0, 3), OPT_STABLE, FIRST_LEAVE_MIRROR),
+    OPT_ROW(STABLE_FACTOR, stable_factor, range(0, 2), OPT_STABLE, FIRST_LEAVE_MIRROR),
+    OPT_DEF(PAD, pad, range(-1, 4096)),
+    OPT_DEF(LP_GRID, lp_grid, range(0, 65536)),
+    OPT_DEF(LP_WIDE, lp_wide, range(-1, 1)),
+    OPT_DEF(BATCH_THREADS, batch_threads, {0, 0, 4, {0, 64, 128, 256}}),
+    OPT_ROW(RESIDENT, resident, range(0, 2), OPT_ELL, FIRST_NOTHING),
+    OPT_ROW(OVERLAP, overlap, range(0, 2), OPT_ELL, FIRST_NOTHING),
+    OPT_ROW(LOOKAHEAD, lookahead, range(1, 32), OPT_ELL, FIRST_NOTHING),
+    OPT_ROW(QUEUE_DEPTH, queue_depth, {0, 0, 2, {0, 48}}, OPT_ELL, FIRST_NOTHING),
+    OPT_OWN(RESIDENT_FAULT, at_least(-1), OPT_ELL),  // ellhip_space::rs_fault_at: per handle only, not inherited by a clone
+    OPT_OWN(RESIDENT_ABANDONED, range(0, -1), OPT_READ_ONLY),
+    OPT_OWN(STABLE_MIRRORED, range(0, -1), OPT_READ_ONLY),
+    OPT_DEF(STAGE_DIRECT, stage_direct, range(0, 1)),  // (per handle: read only, what alloc_common decided)
+    OPT_ROW(APPLY_SYMM, apply_symm, range(0, 1), OPT_ELL, FIRST_NOTHING),
+    OPT_ROW(PACKED_OPERANDS, packed_operands, range(0, 1), OPT_ELL, FIRST_NOTHING),
+};
+#undef OPT_ROW
+#undef OPT_DEF
+#undef OPT_OWN
+
+const OptionRow* option_row(int key) {
+    for (const OptionRow& r : g_option_table)
+        if (r.key == key) return &r;
+    (void)fail(ELLHIP_E_INVALID, "unknown option key");
+    return nullptr;
+}
+long long* option_slot(ellhip_space* s, const OptionRow& r) {  // where a handle keeps the row's value (NULL: it keeps none)
+    return r.opt ? &(s->*r.opt) : r.key == ELLHIP_OPT_RESIDENT_FAULT ? &s->rs_fault_at : nullptr;
+}
+int option_refuse(const OptionRow& r, const char* why) {
+    char buf[256];
+    snprintf(buf, sizeof buf, "%s: %s", r.name, why);
+    return fail(ELLHIP_E_INVALID, buf);
+}
+long long* default_slot(const OptionRow* r) {  // where g_defaults keeps it (NULL, message set: unknown key, or per handle only)
+    if (r && !r->opt && !r->def_only) (void)option_refuse(*r, "not a creation-time default (per handle only)");
+    return !r ? nullptr : r->opt ? &(g_defaults.*r->opt) : r->def_only;
+}
+int option_value_ok(const OptionRow& r, long long v) {
+    const OptAllowed& a = r.allowed;
+    char what[128] = "read only";
+    int len = 0;
+    for (int i = 0; i < a.nset; ++i) {
+        if (a.set[i] == v) return 0;
+        len += snprintf(what + len, sizeof what - (size_t)len, i ? ", %lld" : "value must be one of %lld", a.set[i]);
     }
+    if (a.nset == 0 && v >= a.lo && v <= a.hi) return 0;
+    if (a.nset == 0 && a.hi == OPT_NO_MAX) snprintf(what, sizeof what, "value must be >= %lld", a.lo);
+    else if (a.nset == 0 && a.lo <= a.hi) snprintf(what, sizeof what, "value must be in %lld .. %lld", a.lo, a.hi);
+    return option_refuse(r, what);
+}
+// FIRST_Q_CURRENT, after the value is in place: a lowered threshold may bring the lower-triangle schedule into reach;
+// depth 16 / 24 exist on that schedule only, so where it is gone the handle falls back to depth 8
+int option_schedule_changed(ellhip_space* s) {
+    if (s->defer > 1) {
+        const int rc = symv_alloc(s);
+        if (rc) return rc;
+    }
+    if (s->defer >= 16) {
+        const bool lower = s->symv && s->apply_lower && (s->n % 2) == 0 && s->d_rowpart &&
+                           (s->sharded ? s->shard_symmetric : s->n >= s->symv_min_n);
+        if (!lower) s->defer = 8;
+    }
+    return 0;
 }
 }  // namespace
 
 int ellhip_set_default_option(int key, int64_t value) {
-    int rc = option_ok(key, value);
-    if (rc) return rc;
-    switch (key) {
-        case ELLHIP_OPT_AUTO_DEFER: g_defaults.auto_defer = (int)value; break;
-        case ELLHIP_OPT_SYMV: g_defaults.symv = (int)value; break;
-        case ELLHIP_OPT_SYMV_MIN_N: g_defaults.symv_min_n = value; break;
-        case ELLHIP_OPT_APPLY_LOWER: g_defaults.apply_lower = (int)value; break;
-        case ELLHIP_OPT_APPLY_KERNEL: g_defaults.apply_kernel = (int)value; break;
-        case ELLHIP_OPT_FUSE_DOTS: g_defaults.fuse_dots = (int)value; break;
-        case ELLHIP_OPT_RESIDENT: g_defaults.resident = (int)value; break;
-        case ELLHIP_OPT_OVERLAP: g_defaults.overlap = (int)value; break;
-        case ELLHIP_OPT_LOOKAHEAD: g_defaults.lookahead = (int)value; break;
-        case ELLHIP_OPT_QUEUE_DEPTH: g_defaults.queue_depth = (int)value; break;
-        case ELLHIP_OPT_APPLY_SYMM: g_defaults.apply_symm = (int)value; break;
-        case ELLHIP_OPT_PACKED_OPERANDS: g_defaults.packed_operands = (int)value; break;
-        case ELLHIP_OPT_STABLE_SOLVE: g_defaults.stable_solve = (int)value; break;
-        case ELLHIP_OPT_STABLE_FACTOR: g_defaults.stable_factor = (int)value; break;
-        case ELLHIP_OPT_PAD: g_defaults.pad = (int)value; break;
-        case ELLHIP_OPT_LP_GRID: g_defaults.lp_grid = (int)value; break;
-        case ELLHIP_OPT_LP_WIDE: g_defaults.lp_wide = (int)value; break;
-        case ELLHIP_OPT_BATCH_THREADS: g_defaults.batch_threads = (int)value; break;
-        case ELLHIP_OPT_STAGE_DIRECT: g_defaults.stage_direct = (int)value; break;
-    }
-    return 0;
+    const OptionRow* r = option_row(key);
+    long long* slot = default_slot(r);
+    if (!slot) return ELLHIP_E_INVALID;
+    const int rc = option_value_ok(*r, value);
+    if (!rc) *slot = value;
+    return rc;
 }
 
 int ellhip_default_option(int key, int64_t* value) {
     if (!value) return fail(ELLHIP_E_INVALID, "value is NULL");
-    switch (key) {
-        case ELLHIP_OPT_AUTO_DEFER: *value = g_defaults.auto_defer; break;
-        case ELLHIP_OPT_SYMV: *value = g_defaults.symv; break;
-        case ELLHIP_OPT_SYMV_MIN_N: *value = g_defaults.symv_min_n; break;
-        case ELLHIP_OPT_APPLY_LOWER: *value = g_defaults.apply_lower; break;
-        case ELLHIP_OPT_APPLY_KERNEL: *value = g_defaults.apply_kernel; break;
-        case ELLHIP_OPT_FUSE_DOTS: *value = g_defaults.fuse_dots; break;
-        case ELLHIP_OPT_RESIDENT: *value = g_defaults.resident; break;
-        case ELLHIP_OPT_OVERLAP: *value = g_defaults.overlap; break;
-        case ELLHIP_OPT_LOOKAHEAD: *value = g_defaults.lookahead; break;
-        case ELLHIP_OPT_QUEUE_DEPTH: *value = g_defaults.queue_depth; break;
-        case ELLHIP_OPT_APPLY_SYMM: *value = g_defaults.apply_symm; break;
-        case ELLHIP_OPT_PACKED_OPERANDS: *value = g_defaults.packed_operands; break;
-        case ELLHIP_OPT_STABLE_SOLVE: *value = g_defaults.stable_solve; break;
-        case ELLHIP_OPT_STABLE_FACTOR: *value = g_defaults.stable_factor; break;
-        case ELLHIP_OPT_PAD: *value = g_defaults.pad; break;
-        case ELLHIP_OPT_LP_GRID: *value = g_defaults.lp_grid; break;
-        case ELLHIP_OPT_LP_WIDE: *value = g_defaults.lp_wide; break;
-        case ELLHIP_OPT_BATCH_THREADS: *value = g_defaults.batch_threads; break;
-        case ELLHIP_OPT_STAGE_DIRECT: *value = g_defaults.stage_direct; break;
-        default: return fail(ELLHIP_E_INVALID, "unknown option key");
-    }
+    const long long* slot = default_slot(option_row(key));
+    if (!slot) return ELLHIP_E_INVALID;
+    *value = *slot;
     return 0;
 }
 
 int ellhip_set_option(ellhip_space* s, int key, int64_t value) {
     if (!s) return fail(ELLHIP_E_INVALID, "NULL handle");
-    int rc = option_ok(key, value);
+    const OptionRow* r = option_row(key);
+    if (!r) return ELLHIP_E_INVALID;
+    int rc = option_value_ok(*r, value);
     if (rc) return rc;
     DeviceGuard guard(s->device);
     const bool ell = s->variant == ELLHIP_SPACE_ELL;
-    switch (key) {
-        // chosen per queue run: nothing recorded depends on them
-        case ELLHIP_OPT_RESIDENT:
-            if (!ell) return fail(ELLHIP_E_INVALID, "this option exists on Ell only");
-            s->resident = (int)value;
-            return 0;
-        case ELLHIP_OPT_OVERLAP:
-            if (!ell) return fail(ELLHIP_E_INVALID, "this option exists on Ell only");
-            s->overlap = (int)value;
-            return 0;
-        case ELLHIP_OPT_LOOKAHEAD:
-            if (!ell) return fail(ELLHIP_E_INVALID, "this option exists on Ell only");
-            s->lookahead = (int)value;
-            return 0;
-        case ELLHIP_OPT_QUEUE_DEPTH:
-            if (!ell) return fail(ELLHIP_E_INVALID, "this option exists on Ell only");
-            s->queue_depth = (int)value;
-            return 0;
-        case ELLHIP_OPT_APPLY_SYMM:
-            if (!ell) return fail(ELLHIP_E_INVALID, "this option exists on Ell only");
-            s->apply_symm = (int)value;
-            return 0;
-        case ELLHIP_OPT_PACKED_OPERANDS:
-            if (!ell) return fail(ELLHIP_E_INVALID, "this option exists on Ell only");
-            s->packed_operands = (int)value;
-            return 0;
-        case ELLHIP_OPT_RESIDENT_FAULT:
-            if (!ell) return fail(ELLHIP_E_INVALID, "this option exists on Ell only");
-            s->rs_fault_at = value;
-            return 0;
-        // what has been recorded (and a stale upper triangle) belongs to the schedule in force: Q is made current first
-        case ELLHIP_OPT_SYMV: case ELLHIP_OPT_SYMV_MIN_N: case ELLHIP_OPT_APPLY_LOWER: case ELLHIP_OPT_APPLY_KERNEL:
-        case ELLHIP_OPT_FUSE_DOTS: {
-            if (!ell) return fail(ELLHIP_E_INVALID, "this option exists on Ell only");
-            if (s->in_two_phase) return fail(ELLHIP_E_STATE, "update_begin without update_end");
-            rc = make_q_current(s);
-            if (rc) return rc;
-            if (key == ELLHIP_OPT_SYMV) s->symv = (int)value;
-            else if (key == ELLHIP_OPT_SYMV_MIN_N) s->symv_min_n = value;
-            else if (key == ELLHIP_OPT_APPLY_LOWER) s->apply_lower = (int)value;
-            else if (key == ELLHIP_OPT_APPLY_KERNEL) s->apply_kernel = (int)value;
-            else s->fuse_dots = (int)value;
-            if (s->defer > 1) {
-                rc = symv_alloc(s);  // (a lowered threshold may bring the lower-triangle schedule into reach)
-                if (rc) return rc;
-            }
-            if (s->defer >= 16) {  // depth 16 / 24 exist on the lower-triangle schedule only: fall back to 8 where it is gone
-                const bool lower = s->symv && s->apply_lower && (s->n % 2) == 0 && s->d_rowpart &&
-                                   (s->sharded ? s->shard_symmetric : s->n >= s->symv_min_n);
-                if (!lower) s->defer = 8;
-            }
-            return 0;
-        }
-        case ELLHIP_OPT_STABLE_SOLVE: case ELLHIP_OPT_STABLE_FACTOR:
-            if (ell) return fail(ELLHIP_E_INVALID, "this option exists on EllStable only");
-            rc = stable_mirror_leave(s);  // (the next update enters the layout its options ask for)
-            if (rc) return rc;
-            HIPCHK(hipStreamSynchronize(s->stream));
-            if (key == ELLHIP_OPT_STABLE_SOLVE) s->stable_solve = (int)value; else s->stable_factor = (int)value;
-            return 0;
-        default:
-            return fail(ELLHIP_E_INVALID, "this option is a creation-time default only (ellhip_set_default_option)");
+    if (r->who == OPT_DEFAULT_ONLY) return option_refuse(*r, "this option is a creation-time default only (ellhip_set_default_option)");
+    if (r->who == OPT_ELL && !ell) return option_refuse(*r, "this option exists on Ell only");
+    if (r->who == OPT_STABLE && ell) return option_refuse(*r, "this option exists on EllStable only");
+    long long* slot = option_slot(s, *r);  // (never NULL here: the read-only rows allow no value)
+    if (r->first == FIRST_Q_CURRENT) {
+        if (s->in_two_phase) return fail(ELLHIP_E_STATE, "update_begin without update_end");
+        rc = make_q_current(s);
+        if (rc) return rc;
+        *slot = value;
+        return option_schedule_changed(s);
     }
+    if (r->first == FIRST_LEAVE_MIRROR) {
+        rc = stable_mirror_leave(s);
+        if (rc) return rc;
+        HIPCHK(hipStreamSynchronize(s->stream));
+    }
+    *slot = value;
+    return 0;
 }
 
 int ellhip_get_option(const ellhip_space* s, int key, int64_t* value) {
     if (!s || !value) return fail(ELLHIP_E_INVALID, "NULL argument");
-    switch (key) {
-        case ELLHIP_OPT_SYMV: *value = s->symv; break;
-        case ELLHIP_OPT_SYMV_MIN_N: *value = s->symv_min_n; break;
-        case ELLHIP_OPT_APPLY_LOWER: *value = s->apply_lower; break;
-        case ELLHIP_OPT_APPLY_KERNEL: *value = s->apply_kernel; break;
-        case ELLHIP_OPT_FUSE_DOTS: *value = s->fuse_dots; break;
-        case ELLHIP_OPT_RESIDENT: *value = s->resident; break;
-        case ELLHIP_OPT_OVERLAP: *value = s->overlap; break;
-        case ELLHIP_OPT_LOOKAHEAD: *value = s->lookahead; break;
-        case ELLHIP_OPT_QUEUE_DEPTH: *value = s->queue_depth; break;
-        case ELLHIP_OPT_APPLY_SYMM: *value = s->apply_symm; break;
-        case ELLHIP_OPT_PACKED_OPERANDS: *value = s->packed_operands; break;
-        case ELLHIP_OPT_RESIDENT_FAULT: *value = s->rs_fault_at; break;
-        case ELLHIP_OPT_RESIDENT_ABANDONED: *value = s->rs_abandoned; break;
-        case ELLHIP_OPT_STABLE_SOLVE: *value = s->stable_solve; break;
-        case ELLHIP_OPT_STABLE_FACTOR: *value = s->stable_factor; break;
-        case ELLHIP_OPT_STABLE_MIRRORED: *value = s->st_mirrored ? 1 : 0; break;
-        case ELLHIP_OPT_STAGE_DIRECT: *value = s->stage_direct ? 1 : 0; break;
-        case ELLHIP_OPT_PAD: *value = s->ld - s->n; break;
-        default: return fail(ELLHIP_E_INVALID, "not a per-handle option");
+    switch (key) {  // read only or derived: not a stored value
+        case ELLHIP_OPT_RESIDENT_ABANDONED: *value = s->rs_abandoned; return 0;
+        case ELLHIP_OPT_STABLE_MIRRORED: *value = s->st_mirrored ? 1 : 0; return 0;
+        case ELLHIP_OPT_STAGE_DIRECT: *value = s->stage_direct ? 1 : 0; return 0;
+        case ELLHIP_OPT_PAD: *value = s->ld - s->n; return 0;
     }
+    const OptionRow* r = option_row(key);
+    const long long* slot = r ? option_slot(const_cast<ellhip_space*>(s), *r) : nullptr;
+    if (!slot) return fail(ELLHIP_E_INVALID, "not a per-handle option");
+    *value = *slot;
     return 0;
 }
 
@@ -2831,8 +2754,9 @@ int ellhip_calc(int64_t n, int use_parallel_cut, int kind, double beta0, int has
     if (ellhip_device_count() <= 0) return fail(ELLHIP_E_NODEVICE, "no HIP device");
     if (device < 0 && hipGetDevice(&device) != hipSuccess) device = 0;
     DeviceGuard guard(device);
-    double* d_out = nullptr;
-    HIPCHK(hipMalloc(&d_out, 4 * sizeof(double)));
+    Allocs tmp;
+    double* d_out = nullptr;  // (freed on every return path)
+    HIPCHK(tmp.device(d_out, 4 * sizeof(double)));
     CutParams cp;
     cp.kind = kind;
     cp.has_b1 = has_beta1 ? 1 : 0;
@@ -2842,7 +2766,6 @@ int ellhip_calc(int64_t n, int use_parallel_cut, int kind, double beta0, int has
     double h[4];
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpy(h, d_out, sizeof h, hipMemcpyDeviceToHost);
-    (void)hipFree(d_out);
     if (e != hipSuccess) return fail(ELLHIP_E_HIP, "ellhip_calc", e);
     out3[0] = h[1];
     out3[1] = h[2];
@@ -2880,14 +2803,19 @@ int ellhip_queue_upload(ellhip_space* s, int64_t k, const int32_t* kinds, const 
         hp[(size_t)i].b0 = beta0[i];
         hp[(size_t)i].b1 = (has_beta1 && has_beta1[i] && beta1) ? beta1[i] : 0.0;
     }
-    HIPCHK(hipMalloc(&s->d_qparams, (size_t)k * sizeof(CutParams)));
-    HIPCHK(hipMalloc(&s->d_qgrads, (size_t)k * (size_t)n * sizeof(double)));
-    HIPCHK(hipMalloc(&s->d_qstatus, (size_t)k * sizeof(int)));
-    HIPCHK(hipMalloc(&s->d_qtsq, (size_t)k * sizeof(double)));
-    HIPCHK(hipMemcpy(s->d_qparams, hp.data(), (size_t)k * sizeof(CutParams), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(s->d_qgrads, grads, (size_t)k * (size_t)n * sizeof(double), hipMemcpyHostToDevice));
-    HIPCHK(fill_now(s->d_qstatus, 0xff, (size_t)k * sizeof(int), s->stream));  // -1 = not run yet
-    HIPCHK(fill_now(s->d_qtsq, 0, (size_t)k * sizeof(double), s->stream));
+    // the four buffers and their contents, or no queue at all (qk == 0, every pointer null)
+    hipError_t e = s->mem.device(s->d_qparams, (size_t)k * sizeof(CutParams));
+    if (e == hipSuccess) e = s->mem.device(s->d_qgrads, (size_t)k * (size_t)n * sizeof(double));
+    if (e == hipSuccess) e = s->mem.device(s->d_qstatus, (size_t)k * sizeof(int));
+    if (e == hipSuccess) e = s->mem.device(s->d_qtsq, (size_t)k * sizeof(double));
+    if (e == hipSuccess) e = hipMemcpy(s->d_qparams, hp.data(), (size_t)k * sizeof(CutParams), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(s->d_qgrads, grads, (size_t)k * (size_t)n * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = fill_now(s->d_qstatus, 0xff, (size_t)k * sizeof(int), s->stream);  // -1 = not run yet
+    if (e == hipSuccess) e = fill_now(s->d_qtsq, 0, (size_t)k * sizeof(double), s->stream);
+    if (e != hipSuccess) {
+        queue_free(s);
+        return fail(ELLHIP_E_HIP, "ellhip_queue_upload", e);
+    }
     s->qk = k;
     return 0;
 }

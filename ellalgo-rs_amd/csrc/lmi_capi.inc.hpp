@@ -8,6 +8,7 @@ struct ellhip_lmi {
     int device = 0;
     int mode = 0;  // 0 LMIOracle, 1 LMI0Oracle
     long long n = 0, m = 0;
+    Allocs mem;
     double* d_F = nullptr;
     double* d_B = nullptr;
     double* d_A = nullptr;   // F(x), lower triangle, formed lazily
@@ -67,10 +68,7 @@ void ellhip_lmi_destroy(ellhip_lmi* o) {
     if (!o) return;
     DeviceGuard guard(o->device);
     if (o->stream) (void)hipStreamSynchronize(o->stream);
-    for (double* p : {o->d_F, o->d_B, o->d_A, o->d_S, o->d_x, o->d_v, o->d_g, o->d_partial})
-        if (p) (void)hipFree(p);
-    if (o->d_st) (void)hipFree(o->d_st);
-    if (o->h_st) (void)hipHostFree(o->h_st);
+    o->mem.release_all();
     if (o->stream) (void)hipStreamDestroy(o->stream);
     delete o;
 }
@@ -94,16 +92,16 @@ int ellhip_lmi_create(ellhip_lmi** out, int64_t n, int64_t m, const double* mat_
     DeviceGuard guard(device);
     const size_t mm = (size_t)m * (size_t)m * sizeof(double);
     hipError_t e = hipStreamCreateWithFlags(&o->stream, hipStreamNonBlocking);
-    if (e == hipSuccess && n > 0) e = hipMalloc(&o->d_F, (size_t)n * mm);
-    if (e == hipSuccess && mat_b) e = hipMalloc(&o->d_B, mm);
-    if (e == hipSuccess) e = hipMalloc(&o->d_A, mm);
-    if (e == hipSuccess) e = hipMalloc(&o->d_S, mm);
-    if (e == hipSuccess) e = hipMalloc(&o->d_x, (size_t)(n > 0 ? n : 1) * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc(&o->d_v, (size_t)m * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc(&o->d_g, (size_t)(n > 0 ? n : 1) * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc(&o->d_partial, (size_t)(n > 0 ? n : 1) * LMI_QUAD_CHUNKS * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc(&o->d_st, sizeof(LmiState));
-    if (e == hipSuccess) e = hipHostMalloc(&o->h_st, sizeof(LmiState), hipHostMallocDefault);
+    if (e == hipSuccess && n > 0) e = o->mem.device(o->d_F, (size_t)n * mm);
+    if (e == hipSuccess && mat_b) e = o->mem.device(o->d_B, mm);
+    if (e == hipSuccess) e = o->mem.device(o->d_A, mm);
+    if (e == hipSuccess) e = o->mem.device(o->d_S, mm);
+    if (e == hipSuccess) e = o->mem.device(o->d_x, (size_t)(n > 0 ? n : 1) * sizeof(double));
+    if (e == hipSuccess) e = o->mem.device(o->d_v, (size_t)m * sizeof(double));
+    if (e == hipSuccess) e = o->mem.device(o->d_g, (size_t)(n > 0 ? n : 1) * sizeof(double));
+    if (e == hipSuccess) e = o->mem.device(o->d_partial, (size_t)(n > 0 ? n : 1) * LMI_QUAD_CHUNKS * sizeof(double));
+    if (e == hipSuccess) e = o->mem.device(o->d_st, sizeof(LmiState));
+    if (e == hipSuccess) e = o->mem.pinned(o->h_st, sizeof(LmiState), hipHostMallocDefault);
     if (e == hipSuccess && n > 0) e = hipMemcpy(o->d_F, mat_f, (size_t)n * mm, hipMemcpyHostToDevice);
     if (e == hipSuccess && mat_b) e = hipMemcpy(o->d_B, mat_b, mm, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = fill_now(o->d_S, 0, mm, o->stream);

@@ -15,7 +15,8 @@ struct ellhip_lmi_loop {
     long long n = 0;
     int J = 0;
     bool has_c = false;
-    ellhip_lmi* blocks[LMI_LOOP_JMAX] = {};
+    ellhip_lmi* blocks[LMI_LOOP_JMAX] = {};  // borrowed: the caller's handles
+    Allocs mem;
     double* d_c = nullptr;      // n (optimisation form)
     double* d_x = nullptr;      // n: the point of a single call
     double* d_g = nullptr;      // n: the iteration's gradient
@@ -166,14 +167,7 @@ void ellhip_lmi_loop_destroy(ellhip_lmi_loop* o) {
     if (!o) return;
     DeviceGuard guard(o->device);
     if (o->stream) (void)hipStreamSynchronize(o->stream);
-    for (double* p : {o->d_c, o->d_x, o->d_g, o->d_xbest})
-        if (p) (void)hipFree(p);
-    if (o->d_ls) (void)hipFree(o->d_ls);
-    if (o->d_cp) (void)hipFree(o->d_cp);
-    if (o->d_zero) (void)hipFree(o->d_zero);
-    if (o->h_ls) (void)hipHostFree(o->h_ls);
-    if (o->h_cp) (void)hipHostFree(o->h_cp);
-    if (o->h_vec) (void)hipHostFree(o->h_vec);
+    o->mem.release_all();  // (its own buffers; the blocks are borrowed)
     if (o->stream) (void)hipStreamDestroy(o->stream);
     delete o;
 }
@@ -200,16 +194,16 @@ int ellhip_lmi_loop_create(ellhip_lmi_loop** out, ellhip_lmi* const* blocks, int
     DeviceGuard guard(o->device);
     const size_t vbytes = (size_t)o->n * sizeof(double);
     hipError_t e = hipStreamCreateWithFlags(&o->stream, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipMalloc(&o->d_c, vbytes);
-    if (e == hipSuccess) e = hipMalloc(&o->d_x, vbytes);
-    if (e == hipSuccess) e = hipMalloc(&o->d_g, vbytes);
-    if (e == hipSuccess) e = hipMalloc(&o->d_xbest, vbytes);
-    if (e == hipSuccess) e = hipMalloc(&o->d_ls, sizeof(LmiLoopState));
-    if (e == hipSuccess) e = hipMalloc(&o->d_cp, sizeof(CutParams));
-    if (e == hipSuccess) e = hipMalloc(&o->d_zero, sizeof(int));
-    if (e == hipSuccess) e = hipHostMalloc(&o->h_ls, sizeof(LmiLoopState), hipHostMallocDefault);
-    if (e == hipSuccess) e = hipHostMalloc(&o->h_cp, sizeof(CutParams), hipHostMallocDefault);
-    if (e == hipSuccess) e = hipHostMalloc(&o->h_vec, vbytes, hipHostMallocDefault);
+    if (e == hipSuccess) e = o->mem.device(o->d_c, vbytes);
+    if (e == hipSuccess) e = o->mem.device(o->d_x, vbytes);
+    if (e == hipSuccess) e = o->mem.device(o->d_g, vbytes);
+    if (e == hipSuccess) e = o->mem.device(o->d_xbest, vbytes);
+    if (e == hipSuccess) e = o->mem.device(o->d_ls, sizeof(LmiLoopState));
+    if (e == hipSuccess) e = o->mem.device(o->d_cp, sizeof(CutParams));
+    if (e == hipSuccess) e = o->mem.device(o->d_zero, sizeof(int));
+    if (e == hipSuccess) e = o->mem.pinned(o->h_ls, sizeof(LmiLoopState), hipHostMallocDefault);
+    if (e == hipSuccess) e = o->mem.pinned(o->h_cp, sizeof(CutParams), hipHostMallocDefault);
+    if (e == hipSuccess) e = o->mem.pinned(o->h_vec, vbytes, hipHostMallocDefault);
     if (e == hipSuccess) e = fill_now(o->d_c, 0, vbytes, o->stream);
     if (e == hipSuccess) e = fill_now(o->d_g, 0, vbytes, o->stream);
     if (e == hipSuccess) e = fill_now(o->d_xbest, 0, vbytes, o->stream);

@@ -17,6 +17,7 @@ struct ellhip_lowpass {
     bool nt = false;
     bool wide = false;  // k_lp_scan_wide (4 positions per workgroup step) instead of k_lp_scan (16)
     unsigned grid = 1;
+    Allocs mem;
     double* d_A = nullptr;
     double* d_vals = nullptr;
     double* d_x = nullptr;
@@ -203,17 +204,17 @@ int ellhip_lowpass_create(ellhip_lowpass** out, int64_t ndim, double wpass, doub
     };
     const size_t vbytes = (size_t)ndim * sizeof(double);
     hipError_t e = hipStreamCreateWithFlags(&o->stream, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipMalloc(&o->d_A, (size_t)mdim * (size_t)o->P.ld * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc(&o->d_vals, (size_t)mdim * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc(&o->d_x, vbytes);
-    if (e == hipSuccess) e = hipMalloc(&o->d_g, vbytes);
-    if (e == hipSuccess) e = hipMalloc(&o->d_xbest, vbytes);
-    if (e == hipSuccess) e = hipMalloc(&o->d_ls, sizeof(LpState));
-    if (e == hipSuccess) e = hipMalloc(&o->d_cp, sizeof(CutParams));
-    if (e == hipSuccess) e = hipMalloc(&o->d_zero, sizeof(int));
-    if (e == hipSuccess) e = hipHostMalloc(&o->h_ls, sizeof(LpState), hipHostMallocDefault);
-    if (e == hipSuccess) e = hipHostMalloc(&o->h_cp, sizeof(CutParams), hipHostMallocDefault);
-    if (e == hipSuccess) e = hipHostMalloc(&o->h_vec, vbytes, hipHostMallocDefault);
+    if (e == hipSuccess) e = o->mem.device(o->d_A, (size_t)mdim * (size_t)o->P.ld * sizeof(double));
+    if (e == hipSuccess) e = o->mem.device(o->d_vals, (size_t)mdim * sizeof(double));
+    if (e == hipSuccess) e = o->mem.device(o->d_x, vbytes);
+    if (e == hipSuccess) e = o->mem.device(o->d_g, vbytes);
+    if (e == hipSuccess) e = o->mem.device(o->d_xbest, vbytes);
+    if (e == hipSuccess) e = o->mem.device(o->d_ls, sizeof(LpState));
+    if (e == hipSuccess) e = o->mem.device(o->d_cp, sizeof(CutParams));
+    if (e == hipSuccess) e = o->mem.device(o->d_zero, sizeof(int));
+    if (e == hipSuccess) e = o->mem.pinned(o->h_ls, sizeof(LpState), hipHostMallocDefault);
+    if (e == hipSuccess) e = o->mem.pinned(o->h_cp, sizeof(CutParams), hipHostMallocDefault);
+    if (e == hipSuccess) e = o->mem.pinned(o->h_vec, vbytes, hipHostMallocDefault);
     if (e != hipSuccess) return bail(fail(e == hipErrorOutOfMemory ? ELLHIP_E_NOMEM : ELLHIP_E_HIP, "lowpass allocation", e));
     if (o->P.ld != ndim) e = fill_now(o->d_A, 0, (size_t)mdim * (size_t)o->P.ld * sizeof(double), o->stream);
     if (e == hipSuccess) e = fill_now(o->d_vals, 0, (size_t)mdim * sizeof(double), o->stream);
@@ -266,17 +267,7 @@ void ellhip_lowpass_destroy(ellhip_lowpass* o) {
     if (!o) return;
     DeviceGuard guard(o->device);
     if (o->stream) (void)hipStreamSynchronize(o->stream);
-    if (o->d_A) (void)hipFree(o->d_A);
-    if (o->d_vals) (void)hipFree(o->d_vals);
-    if (o->d_x) (void)hipFree(o->d_x);
-    if (o->d_g) (void)hipFree(o->d_g);
-    if (o->d_xbest) (void)hipFree(o->d_xbest);
-    if (o->d_ls) (void)hipFree(o->d_ls);
-    if (o->d_cp) (void)hipFree(o->d_cp);
-    if (o->d_zero) (void)hipFree(o->d_zero);
-    if (o->h_ls) (void)hipHostFree(o->h_ls);
-    if (o->h_cp) (void)hipHostFree(o->h_cp);
-    if (o->h_vec) (void)hipHostFree(o->h_vec);
+    o->mem.release_all();
     if (o->stream) (void)hipStreamDestroy(o->stream);
     delete o;
 }

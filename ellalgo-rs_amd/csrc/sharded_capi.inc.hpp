@@ -120,6 +120,7 @@ struct ellhip_sharded {
     // group runs of symmetric shards: 0 = not decided yet, 1 = EVERY rank holds the group buffers, -1 = some rank could not
     // allocate them: every rank takes the cut-by-cut schedule (decided once, collectively: shard_group_agree)
     int group_state = 0;
+    Allocs mem;
     double* d_agree = nullptr;
 };
 
@@ -302,8 +303,11 @@ void ellhip_sharded_destroy(ellhip_sharded* s) {
         Rccl* r = rccl();
         if (r->CommDestroy) (void)r->CommDestroy(s->comm);
     }
-    if (s->d_agree) (void)hipFree(s->d_agree);
-    if (s->sh) ellhip_destroy(s->sh);
+    if (s->sh) {
+        DeviceGuard guard(s->sh->device);
+        s->mem.release_all();
+        ellhip_destroy(s->sh);
+    }
     delete s;
 }
 
@@ -390,7 +394,7 @@ int shard_group_agree(ellhip_sharded* s) {
     double ok = (mrc == 0) ? 1.0 : 0.0, sum = ok;
     if (s->nranks > 1) {
         DeviceGuard guard(s->sh->device);
-        if (!s->d_agree) HIPCHK(hipMalloc(&s->d_agree, sizeof(double)));
+        if (!s->d_agree) HIPCHK(s->mem.device(s->d_agree, sizeof(double)));
         HIPCHK(hipMemcpyAsync(s->d_agree, &ok, sizeof(double), hipMemcpyHostToDevice, s->sh->stream));
         const int xrc = shard_group_exchange(s, s->d_agree, 1, s->sh->stream);
         if (xrc) return xrc;

@@ -12,6 +12,7 @@ struct ellhip_svm {
     SvmParams P{};
     bool nt = false;
     unsigned grid = 1;
+    Allocs mem;
     double* d_XT = nullptr;     // nfeat x ld, feature-major
     int* d_labels = nullptr;    // m
     SvmPartial* d_part = nullptr;  // grid
@@ -125,18 +126,18 @@ int ellhip_svm_create(ellhip_svm** out, int64_t m, int64_t nfeat, const double* 
     const size_t vbytes = (size_t)n * sizeof(double);
     const size_t tbytes = (size_t)nfeat * (size_t)o->P.ld * sizeof(double);
     hipError_t e = hipStreamCreateWithFlags(&o->stream, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipMalloc(&o->d_XT, tbytes);
-    if (e == hipSuccess) e = hipMalloc(&o->d_labels, (size_t)m * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc(&o->d_part, (size_t)o->grid * sizeof(SvmPartial));
-    if (e == hipSuccess) e = hipMalloc(&o->d_x, vbytes);
-    if (e == hipSuccess) e = hipMalloc(&o->d_g, vbytes);
-    if (e == hipSuccess) e = hipMalloc(&o->d_xbest, vbytes);
-    if (e == hipSuccess) e = hipMalloc(&o->d_ss, sizeof(SvmState));
-    if (e == hipSuccess) e = hipMalloc(&o->d_cp, sizeof(CutParams));
-    if (e == hipSuccess) e = hipMalloc(&o->d_zero, sizeof(int));
-    if (e == hipSuccess) e = hipHostMalloc(&o->h_ss, sizeof(SvmState), hipHostMallocDefault);
-    if (e == hipSuccess) e = hipHostMalloc(&o->h_cp, sizeof(CutParams), hipHostMallocDefault);
-    if (e == hipSuccess) e = hipHostMalloc(&o->h_vec, vbytes, hipHostMallocDefault);
+    if (e == hipSuccess) e = o->mem.device(o->d_XT, tbytes);
+    if (e == hipSuccess) e = o->mem.device(o->d_labels, (size_t)m * sizeof(int));
+    if (e == hipSuccess) e = o->mem.device(o->d_part, (size_t)o->grid * sizeof(SvmPartial));
+    if (e == hipSuccess) e = o->mem.device(o->d_x, vbytes);
+    if (e == hipSuccess) e = o->mem.device(o->d_g, vbytes);
+    if (e == hipSuccess) e = o->mem.device(o->d_xbest, vbytes);
+    if (e == hipSuccess) e = o->mem.device(o->d_ss, sizeof(SvmState));
+    if (e == hipSuccess) e = o->mem.device(o->d_cp, sizeof(CutParams));
+    if (e == hipSuccess) e = o->mem.device(o->d_zero, sizeof(int));
+    if (e == hipSuccess) e = o->mem.pinned(o->h_ss, sizeof(SvmState), hipHostMallocDefault);
+    if (e == hipSuccess) e = o->mem.pinned(o->h_cp, sizeof(CutParams), hipHostMallocDefault);
+    if (e == hipSuccess) e = o->mem.pinned(o->h_vec, vbytes, hipHostMallocDefault);
     if (e != hipSuccess) return bail(fail(e == hipErrorOutOfMemory ? ELLHIP_E_NOMEM : ELLHIP_E_HIP, "svm allocation", e));
     if (o->P.ld != m) e = fill_now(o->d_XT, 0, tbytes, o->stream);  // the padding samples read as 0 and are never used
     if (e == hipSuccess) e = fill_now(o->d_zero, 0, sizeof(int), o->stream);
@@ -146,8 +147,9 @@ int ellhip_svm_create(ellhip_svm** out, int64_t m, int64_t nfeat, const double* 
     // the table: bounded slabs of the caller's rows into one staging buffer, transposed on the device (peak device
     // memory is the table plus one slab; no host transpose)
     const long long slab_rows = std::max<long long>(1, std::min<long long>(m, (64LL << 20) / (nfeat * 8)));
+    Allocs slab;  // (gone on every return path)
     double* d_slab = nullptr;
-    e = hipMalloc(&d_slab, (size_t)slab_rows * (size_t)nfeat * sizeof(double));
+    e = slab.device(d_slab, (size_t)slab_rows * (size_t)nfeat * sizeof(double));
     if (e != hipSuccess) return bail(fail(e == hipErrorOutOfMemory ? ELLHIP_E_NOMEM : ELLHIP_E_HIP, "svm staging allocation", e));
     for (long long r0 = 0; r0 < m && e == hipSuccess; r0 += slab_rows) {
         const long long rows = std::min(m - r0, slab_rows);
@@ -160,7 +162,7 @@ int ellhip_svm_create(ellhip_svm** out, int64_t m, int64_t nfeat, const double* 
         e = hipGetLastError();
         if (e == hipSuccess) e = hipStreamSynchronize(o->stream);  // the slab is overwritten next
     }
-    (void)hipFree(d_slab);
+    slab.release_all();
     if (e != hipSuccess) return bail(fail(ELLHIP_E_HIP, "svm table upload", e));
     SvmState ss;
     memset(&ss, 0, sizeof ss);
@@ -176,19 +178,7 @@ void ellhip_svm_destroy(ellhip_svm* o) {
     if (!o) return;
     DeviceGuard guard(o->device);
     if (o->stream) (void)hipStreamSynchronize(o->stream);
-    if (o->d_XT) (void)hipFree(o->d_XT);
-    if (o->d_labels) (void)hipFree(o->d_labels);
-    if (o->d_part) (void)hipFree(o->d_part);
-    if (o->d_x) (void)hipFree(o->d_x);
-    if (o->d_g) (void)hipFree(o->d_g);
-    if (o->d_xbest) (void)hipFree(o->d_xbest);
-    if (o->d_margins) (void)hipFree(o->d_margins);
-    if (o->d_ss) (void)hipFree(o->d_ss);
-    if (o->d_cp) (void)hipFree(o->d_cp);
-    if (o->d_zero) (void)hipFree(o->d_zero);
-    if (o->h_ss) (void)hipHostFree(o->h_ss);
-    if (o->h_cp) (void)hipHostFree(o->h_cp);
-    if (o->h_vec) (void)hipHostFree(o->h_vec);
+    o->mem.release_all();
     if (o->stream) (void)hipStreamDestroy(o->stream);
     delete o;
 }
@@ -218,7 +208,7 @@ int ellhip_svm_margins(ellhip_svm* o, const double* x, double* margins_out) {
     DeviceGuard guard(o->device);
     const size_t mbytes = (size_t)o->P.m * sizeof(double);
     if (!o->d_margins) {
-        const hipError_t e = hipMalloc(&o->d_margins, mbytes);
+        const hipError_t e = o->mem.device(o->d_margins, mbytes);
         if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? ELLHIP_E_NOMEM : ELLHIP_E_HIP, "svm margins allocation", e);
     }
     int rc = svm_upload_x(o, x);
