@@ -154,3 +154,12 @@ class EllBatchStreamed(EllBatch):
         v = int(self._lib.ellhip_batch_is_streamed(self._h))
         capi.check(min(v, 0), "ellhip_batch_is_streamed")
         return bool(v)
+
+
+class EllStableBatchStreamed(EllStableBatch):
+    """B `EllStable` spaces of one dimension n <= 1024 with the packed buffers streamed from HBM
+    (include/ellhip_batch_streamed_stable.h): the same calls and the same bits as `EllStableBatch`, past its n = 128.
+    Every batched cutting-plane loop refuses it."""
+    _create = "ellhip_batch_create_streamed_stable"
+    _from_space = "ellhip_batch_streamed_stable_from_space"
+    is_streamed = EllBatchStreamed.is_streamed

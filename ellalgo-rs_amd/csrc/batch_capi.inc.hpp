@@ -17,8 +17,9 @@ struct ellhip_batch {
     int no_defer_trick = 0;
     int use_parallel_cut = 1;
     Allocs mem;
-    int streamed = 0;      // made by ellhip_batch_create_streamed / _streamed_from_space: k_batch_streamed_update, Q stays in HBM
-    int* d_sym = nullptr;  // streamed only: [B], 1 = that matrix is symmetric to the bit (batch_streamed_kernels.hpp)
+    int streamed = 0;      // made by a streamed constructor: Q stays in HBM (Ell: k_batch_streamed_update; EllStable:
+                           // k_batch_streamed_update_stable, scratch triangle at bss_scratch_slot)
+    int* d_sym = nullptr;  // streamed Ell only: [B], 1 = that matrix is symmetric to the bit (batch_streamed_kernels.hpp)
     double* d_Q = nullptr;
     double* d_xc = nullptr;
     double* d_kappa = nullptr;
@@ -67,8 +68,14 @@ int batch_shape_stable(ellhip_batch* h) {
 int batch_streamed_shape(ellhip_batch* h);
 int batch_streamed_launch(ellhip_batch* h, long long K, const int* kinds, const double* grads, const double* b0, const int* hb1,
                           const double* b1, int* status, double* tsq_out);
+// batch_streamed_stable_capi.inc.hpp
+int batch_streamed_stable_shape(ellhip_batch* h);
+int batch_streamed_stable_launch(ellhip_batch* h, long long K, const int* kinds, const double* grads, const double* b0,
+                                 const int* hb1, const double* b1, int* status, double* tsq_out);
+int batch_streamed_stable_rotate(ellhip_batch* h);
 
 int batch_shape(ellhip_batch* h) {
+    if (h->streamed && h->variant == ELLHIP_SPACE_ELL_STABLE) return batch_streamed_stable_shape(h);
     if (h->streamed) return batch_streamed_shape(h);
     if (h->variant == ELLHIP_SPACE_ELL_STABLE) return batch_shape_stable(h);
     h->T = h->n <= 64 ? 256 : 128;
@@ -108,6 +115,8 @@ int batch_shape(ellhip_batch* h) {
 
 int batch_launch(ellhip_batch* h, long long K, const int* kinds, const double* grads, const double* b0, const int* hb1,
                  const double* b1, int* status, double* tsq_out) {
+    if (h->streamed && h->variant == ELLHIP_SPACE_ELL_STABLE)
+        return batch_streamed_stable_launch(h, K, kinds, grads, b0, hb1, b1, status, tsq_out);
     if (h->streamed) return batch_streamed_launch(h, K, kinds, grads, b0, hb1, b1, status, tsq_out);
     BatchParams P;
     P.B = h->B;
@@ -159,7 +168,7 @@ int batch_new(ellhip_batch** out, long long B, long long n, int device, int vari
     DeviceGuard guard(device);
     int rc = batch_shape(h);
     if (!rc) rc = batch_alloc(h);
-    if (!rc && streamed && h->mem.device(h->d_sym, (size_t)B * sizeof(int)) != hipSuccess)
+    if (!rc && streamed && variant == ELLHIP_SPACE_ELL && h->mem.device(h->d_sym, (size_t)B * sizeof(int)) != hipSuccess)
         rc = fail(ELLHIP_E_NOMEM, "streamed batch engine: flags");
     if (rc) {
         ellhip_batch_destroy(h);
@@ -366,10 +375,23 @@ void* ellhip_batch_stream(ellhip_batch* h) { return h ? (void*)h->stream : nullp
         return 0;                                                                                       \
     }
 BATCH_GET(ellhip_batch_get_xc, d_xc, h->B * h->n)
-BATCH_GET(ellhip_batch_get_mq, d_Q, h->B * h->n * h->n)
 BATCH_GET(ellhip_batch_get_kappa, d_kappa, h->B)
 BATCH_GET(ellhip_batch_get_tsq, d_tsq, h->B)
 #undef BATCH_GET
+
+int ellhip_batch_get_mq(ellhip_batch* h, double* out) {
+    if (!h || !out) return fail(ELLHIP_E_INVALID, "NULL argument");
+    DeviceGuard guard(h->device);
+    HIPCHK(hipStreamSynchronize(h->stream));
+    // a streamed EllStable handle keeps the scratch triangle in its own order: the reference's for the copy, then back
+    const bool rotated = h->streamed && h->variant == ELLHIP_SPACE_ELL_STABLE;
+    if (rotated) {
+        const int rc = batch_streamed_stable_rotate(h);
+        if (rc) return rc;
+    }
+    HIPCHK(hipMemcpy(out, h->d_Q, (size_t)h->B * h->n * h->n * sizeof(double), hipMemcpyDeviceToHost));
+    return rotated ? batch_streamed_stable_rotate(h) : 0;
+}
 
 int ellhip_batch_set_xc(ellhip_batch* h, const double* xc) {
     if (!h || !xc) return fail(ELLHIP_E_INVALID, "NULL argument");

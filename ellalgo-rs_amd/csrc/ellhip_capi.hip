@@ -2963,6 +2963,7 @@ int ellhip_profile_read(ellhip_space* s, double* ms_out, int64_t* count_out) {
 #include "lowpass_capi.inc.hpp"
 #include "batch_capi.inc.hpp"
 #include "batch_streamed_capi.inc.hpp"
+#include "batch_streamed_stable_capi.inc.hpp"
 #include "lmi_capi.inc.hpp"
 #include "sharded_capi.inc.hpp"
 #include "svm_capi.inc.hpp"

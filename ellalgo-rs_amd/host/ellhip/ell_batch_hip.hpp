@@ -4,7 +4,8 @@
 // the CPU arithmetic.  `from_space` makes B clones of one EllHip (BSearchAdaptor's clone per probe,
 // src/cutting_plane.rs:410).  EllStableBatchHip is the same for a `Vec<EllStable>` (clones of one EllStableHip).
 // EllBatchStreamedHip is a `Vec<Ell>` of one dimension n <= 1024 on the streamed engine (include/ellhip_batch_streamed.h):
-// the same calls and the same bits, the matrices streamed from HBM instead of held in LDS.
+// the same calls and the same bits, the matrices streamed from HBM instead of held in LDS.  EllStableBatchStreamedHip is the
+// same for a `Vec<EllStable>` (include/ellhip_batch_streamed_stable.h; clones of one EllStableHip).
 #pragma once
 
 #include <cstdint>
@@ -12,13 +13,14 @@
 
 #include "../../../include/ellhip_batch.h"
 #include "../../../include/ellhip_batch_streamed.h"
+#include "../../../include/ellhip_batch_streamed_stable.h"
 #include "ell_hip.hpp"
 
 namespace ellhip {
 
 template <int VARIANT, bool STREAMED = false>
 class BatchHip {
-    static_assert(!STREAMED || VARIANT == ELLHIP_SPACE_ELL, "the streamed engine holds Ell spaces only");
+    static constexpr bool STABLE = VARIANT == ELLHIP_SPACE_ELL_STABLE;
 
   public:
     // Ell::new_with_scalar(val[b], xc[b]) for every b (src/ell.rs:71-73; EllStable: src/ell_stable.rs:33-35)
@@ -37,9 +39,12 @@ class BatchHip {
     template <int SPACE>
     static BatchHip from_space(SpaceHip<SPACE>& space, std::size_t B) {
         BatchHip r;
-        if (STREAMED)
+        if (STREAMED && STABLE)
+            check(ellhip_batch_streamed_stable_from_space(&r.h_, space.handle(), (int64_t)B),
+                  "ellhip_batch_streamed_stable_from_space");
+        else if (STREAMED)
             check(ellhip_batch_streamed_from_space(&r.h_, space.handle(), (int64_t)B), "ellhip_batch_streamed_from_space");
-        else if (VARIANT == ELLHIP_SPACE_ELL_STABLE)
+        else if (STABLE)
             check(ellhip_batch_stable_from_space(&r.h_, space.handle(), (int64_t)B), "ellhip_batch_stable_from_space");
         else
             check(ellhip_batch_from_space(&r.h_, space.handle(), (int64_t)B), "ellhip_batch_from_space");
@@ -107,11 +112,12 @@ class BatchHip {
         Arr fm, fd;
         if (mq) fm = flatten(*mq, n_ * n_);
         if (diag) fd = flatten(*diag, n_);
-        const bool stable = VARIANT == ELLHIP_SPACE_ELL_STABLE;
-        check((STREAMED ? ellhip_batch_create_streamed : stable ? ellhip_batch_create_stable : ellhip_batch_create)(
+        check((STREAMED ? (STABLE ? ellhip_batch_create_streamed_stable : ellhip_batch_create_streamed)
+                        : (STABLE ? ellhip_batch_create_stable : ellhip_batch_create))(
                   &h_, (int64_t)B_, (int64_t)n_, kappa ? kappa->data() : nullptr, mq ? fm.data() : nullptr,
                   diag ? fd.data() : nullptr, fx.data(), device),
-              STREAMED ? "ellhip_batch_create_streamed" : stable ? "ellhip_batch_create_stable" : "ellhip_batch_create");
+              STREAMED ? (STABLE ? "ellhip_batch_create_streamed_stable" : "ellhip_batch_create_streamed")
+                       : (STABLE ? "ellhip_batch_create_stable" : "ellhip_batch_create"));
     }
     Arr flatten(const std::vector<Arr>& v, std::size_t each) const {
         if (v.size() != B_) throw Error(ELLHIP_E_INVALID, "need one entry per ellipsoid");
@@ -158,5 +164,6 @@ class BatchHip {
 using EllBatchHip = BatchHip<ELLHIP_SPACE_ELL>;
 using EllStableBatchHip = BatchHip<ELLHIP_SPACE_ELL_STABLE>;
 using EllBatchStreamedHip = BatchHip<ELLHIP_SPACE_ELL, true>;
+using EllStableBatchStreamedHip = BatchHip<ELLHIP_SPACE_ELL_STABLE, true>;
 
 }  // namespace ellhip

@@ -23,8 +23,8 @@
  * A matrix given by the caller that is not symmetric to the bit is read along its true rows (uncoalesced, slower) until
  * its first successful cut has mirrored it.
  *
- * Not offered: EllStable, n > 1024, sharding.  Same conventions as ellhip.h: 0 = ok, negative = ELLHIP_E_*, no CPU
- * fallback.
+ * EllStable on this engine: ellhip_batch_streamed_stable.h.  Not offered: n > 1024, sharding.  Same conventions as
+ * ellhip.h: 0 = ok, negative = ELLHIP_E_*, no CPU fallback.
  */
 #ifndef ELLHIP_BATCH_STREAMED_H
 #define ELLHIP_BATCH_STREAMED_H
@@ -44,7 +44,8 @@ int ellhip_batch_create_streamed(ellhip_batch **out, int64_t B, int64_t n, const
                                  const double *diag, const double *xc, int device);
 /* B clones of one unsharded Ell handle of dimension <= 1024, as ellhip_batch_from_space.  EllStable handles are refused. */
 int ellhip_batch_streamed_from_space(ellhip_batch **out, const ellhip_space *space, int64_t B);
-/* 1 for a handle made by one of the two constructors above, 0 for any other batch handle; negative = ELLHIP_E_* */
+/* 1 for a handle made by one of the two constructors above or by those of ellhip_batch_streamed_stable.h, 0 for any other
+ * batch handle; negative = ELLHIP_E_* */
 int ellhip_batch_is_streamed(const ellhip_batch *h);
 
 #ifdef __cplusplus

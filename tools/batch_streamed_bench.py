@@ -20,6 +20,18 @@ every form from fresh handles and the states (Q, xc, kappa) must agree with the 
 inf-norm); the LDS engine must agree to the bit.
 
     python3 tools/batch_streamed_bench.py [--sizes 128,129,256,512,1024] [--seconds 1.0] [--reps 3] [--out F]
+
+--space stable measures EllStable on the same engine (include/ellhip_batch_streamed_stable.h) instead:
+for each n of --sizes (default 256,512,1024) and each B of --batches (default 64,512), B `EllStable` spaces from the identity,
+the same central cuts, K = 8 per launch.  Three forms alternate inside every repetition: the streamed EllStable batch, the
+streamed Ell batch of the same shape (for scale), and the baseline -- 16 single `EllStable` handles of the same n that receive
+the cuts of ellipsoids 0..15 through ellhip_update, one after another (what B spaces of this size had to use before; its rate
+per update does not depend on how many handles take turns, except that 16 of them stay in the Infinity Cache where B = 512
+would not, which favours the baseline).  bytes_per_update is the byte model of a successful cut, 24 n^2 + 48 n + 24: the factor
+read 4 n^2, the scratch triangle written 4 n^2 and read twice 8 n^2, the factor read and written 8 n^2.  Before any rate, 8 cuts
+on 16 ellipsoids by the batch and by the single handles must agree within 1e-10 in xc, kappa, the diagonal and the factor.
+
+    python3 tools/batch_streamed_bench.py --space stable [--sizes 256,512,1024] [--batches 64,512] [--out F]
 """
 import argparse
 import ctypes as C
@@ -224,9 +236,85 @@ def run_population(pkg, n, name, nbytes, cached, args, emit):
         dev.free()
 
 
+def stable_singles(pkg, n, grads16):
+    """16 single EllStable handles and the step that gives each the 8 cuts of its ellipsoid through ellhip_update"""
+    hs = [pkg.EllStable.new_with_scalar(1.0, np.zeros(n)) for _ in range(NSINGLE)]
+
+    def step():
+        for k in range(KMAX):
+            for h, s in enumerate(hs):
+                if int(s._update(1, (grads16[k, h], 0.0))) != 0:
+                    raise RuntimeError("ellhip_update: a central cut did not succeed")
+
+    return hs, step
+
+
+def verify_stable(pkg, n, grads16):
+    """8 cuts on 16 ellipsoids by the streamed EllStable batch (K = 8 and K = 1) and by single handles from fresh state"""
+    z = np.zeros((NSINGLE, n))
+    kinds = np.full((KMAX, NSINGLE), 1, dtype=np.int32)
+    b0 = np.zeros((KMAX, NSINGLE))
+    ref = pkg.EllStableBatchStreamed.new_with_scalar(1.0, z)
+    st, _ = ref.update(kinds, grads16, b0)
+    one = pkg.EllStableBatchStreamed.new_with_scalar(1.0, z)
+    for k in range(KMAX):
+        s1, _ = one.update(kinds[k], grads16[k], b0[k])
+        st = np.concatenate([st, s1])
+    if not (st == 0).all():
+        raise RuntimeError("verify: a central cut did not succeed")
+    q, x, kap = ref.mq, ref.xc(), ref.kappa
+    if not (np.array_equal(one.mq, q) and np.array_equal(one.xc(), x) and np.array_equal(one.kappa, kap)):
+        raise RuntimeError("verify: K = 1 and K = 8 differ in a bit")
+    hs, step = stable_singles(pkg, n, grads16)
+    step()
+    worst = {"ellhip_update": max(max(rel_inf(np.triu(s.mq), np.triu(q[h])), rel_inf(s.xc(), x[h]),
+                                      abs(s.kappa - kap[h]) / abs(kap[h])) for h, s in enumerate(hs))}
+    if not worst["ellhip_update"] <= TOL:
+        raise RuntimeError(f"verify n={n}: single EllStable handles differ from the streamed batch by more than {TOL}: {worst}")
+    return worst
+
+
+def run_stable(pkg, n, B, args, emit):
+    rng = np.random.default_rng(0x5EED + n)
+    dev = DevArrays(pkg, B, n, rng)
+    try:
+        grads16 = np.ascontiguousarray(dev.grads[:, :NSINGLE])
+        worst = verify_stable(pkg, n, grads16)
+        stable = pkg.EllStableBatchStreamed.new_with_scalar(1.0, np.zeros((B, n)))
+        ell = pkg.EllBatchStreamed.new_with_scalar(1.0, np.zeros((B, n)))
+        hs, step = stable_singles(pkg, n, grads16)
+        forms = {"streamed_stable_k8": (lambda: dev.launch(stable, KMAX), stable.synchronize, KMAX * B),
+                 "streamed_ell_k8": (lambda: dev.launch(ell, KMAX), ell.synchronize, KMAX * B),
+                 "sequential_ellhip_update": (step, lambda: None, KMAX * NSINGLE)}
+        rates = {f: [] for f in forms}
+        for _ in range(args.reps):
+            for f, (go, sync, per_step) in forms.items():  # the forms alternate inside every repetition
+                rates[f].append(window(go, sync, per_step, args.seconds))
+                if f.startswith("streamed"):
+                    dev.check_status(KMAX, f)
+        if not (np.isfinite(stable.tsq()).all() and np.isfinite(ell.tsq()).all()):
+            raise RuntimeError(f"n={n}: non-finite tsq")
+        r, e, b = (stats(rates[f]) for f in forms)
+        bpu = 24.0 * n * n + 48.0 * n + 24.0
+        emit({"workload": f"ellstable-batch-streamed-n{n}-b{B}-k{KMAX}", "n": n, "ellipsoids": B, "cuts_per_launch": KMAX,
+              "population_bytes": B * 8 * n * n, "updates_per_s": r, "bytes_per_update": bpu,
+              "byte_model_bytes_per_s": bpu * r["median"], "hbm_peak_frac": bpu * r["median"] / HBM_PEAK_BS,
+              "streamed_ell": {"updates_per_s": e}, "ratio_vs_streamed_ell": r["median"] / e["median"],
+              "baseline": {"form": f"sequential_ellhip_update ({NSINGLE} single EllStable handles, one after another)",
+                           "updates_per_s": b},
+              "ratio_vs_baseline": r["median"] / b["median"],
+              "figure": "whole launch (wall clock, inputs resident, ellhip_batch_update_dev), not a kernel's share",
+              "window_seconds": args.seconds, "repetitions": args.reps, "cuts": "central, seeded normal gradients",
+              "verified_rel_err": worst})
+    finally:
+        dev.free()
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.splitlines()[0])
-    ap.add_argument("--sizes", default="128,129,256,512,1024")
+    ap.add_argument("--space", choices=("ell", "stable"), default="ell")
+    ap.add_argument("--batches", default="64,512", help="--space stable: ellipsoids per batch")
+    ap.add_argument("--sizes", default=None, help="default 128,129,256,512,1024 (--space stable: 256,512,1024)")
     ap.add_argument("--seconds", type=float, default=1.0, help="length of a timed window (at least)")
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--populations", default="64MiB,4GiB")
@@ -245,6 +333,13 @@ def main():
             with open(args.out, "a") as f:
                 f.write(line + "\n")
 
+    if args.sizes is None:
+        args.sizes = "256,512,1024" if args.space == "stable" else "128,129,256,512,1024"
+    if args.space == "stable":
+        for n in (int(s) for s in args.sizes.split(",")):
+            for B in (int(s) for s in args.batches.split(",")):
+                run_stable(pkg, n, max(B, NSINGLE), args, emit)
+        return
     for n in (int(s) for s in args.sizes.split(",")):
         for name, nbytes, cached in POPULATIONS:
             if name in args.populations.split(","):
