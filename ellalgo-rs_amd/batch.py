@@ -159,7 +159,8 @@ class EllBatchStreamed(EllBatch):
 class EllStableBatchStreamed(EllStableBatch):
     """B `EllStable` spaces of one dimension n <= 1024 with the packed buffers streamed from HBM
     (include/ellhip_batch_streamed_stable.h): the same calls and the same bits as `EllStableBatch`, past its n = 128.
-    Every batched cutting-plane loop refuses it."""
+    Of the batched cutting-plane loops the low-pass one runs on it (`BatchLowpassProblem.streamed`,
+    include/ellhip_batch_lowpass_streamed_stable.h); the others refuse it."""
     _create = "ellhip_batch_create_streamed_stable"
     _from_space = "ellhip_batch_streamed_stable_from_space"
     is_streamed = EllBatchStreamed.is_streamed

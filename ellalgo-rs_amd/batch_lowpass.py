@@ -3,7 +3,8 @@ independent `LowpassOracle`s (src/oracles/lowpass_oracle.rs) of one filter lengt
 ripple limits and round-robin cursors and its own ellipsoid of an `EllBatch` or an `EllStableBatch`
 (include/ellhip_batch_stable_loops.h), over one shared 15n x n table; solved by one kernel per chunk of iterations.
 `BatchLowpassProblem.streamed` (include/ellhip_batch_lowpass_streamed.h) takes n up to 1024 and solves on an
-`EllBatchStreamed`.  Bit-identical to the CPU arithmetic."""
+`EllBatchStreamed` or an `EllStableBatchStreamed` (include/ellhip_batch_lowpass_streamed_stable.h).  Bit-identical to the
+CPU arithmetic."""
 from __future__ import annotations
 
 import ctypes as C
@@ -18,8 +19,11 @@ STATE_DOUBLES = ("fmax", "sp_sq")
 
 
 def _loop_entry(batch, name: str) -> str:
-    """the `_streamed` entry point for an EllBatchStreamed, else what capi.batch_loop_entry chooses"""
-    return name + "_streamed" if getattr(batch, "is_streamed", False) else capi.batch_loop_entry(batch, name)
+    """the `_streamed` entry point for an EllBatchStreamed, `_streamed_stable`
+    (include/ellhip_batch_lowpass_streamed_stable.h) for an EllStableBatchStreamed, else what capi.batch_loop_entry chooses"""
+    if not getattr(batch, "is_streamed", False):
+        return capi.batch_loop_entry(batch, name)
+    return name + ("_streamed_stable" if batch.variant == capi.SPACE_ELL_STABLE else "_streamed")
 
 
 class BatchLowpassProblem:
@@ -41,7 +45,7 @@ class BatchLowpassProblem:
     @classmethod
     def streamed(cls, n: int, wpass, wstop, lp_sq, up_sq, sp_sq, spectrum=None, *, device: int = -1):
         """The same problems for 1 <= n <= 1024 (include/ellhip_batch_lowpass_streamed.h): `optim` / `feas` then take an
-        `EllBatchStreamed`.  The table is kept twice in HBM, 2 * 15 n^2 * 8 bytes: 240 MiB at n = 1024."""
+        `EllBatchStreamed` or an `EllStableBatchStreamed`.  The table is kept twice in HBM, 2 * 15 n^2 * 8 bytes: 240 MiB at n = 1024."""
         return cls(n, wpass, wstop, lp_sq, up_sq, sp_sq, spectrum, device=device,
                    _create="ellhip_batch_lowpass_create_streamed")
 
@@ -102,7 +106,8 @@ class BatchLowpassProblem:
         return grad, beta0, has1, beta1, shrunk, gamma, rc
 
     def optim(self, batch, gamma, max_iters: int, tol: float):
-        """cutting_plane_optim per problem on `batch` (an EllBatch, an EllStableBatch or an EllBatchStreamed).  Returns
+        """cutting_plane_optim per problem on `batch` (an EllBatch, an EllStableBatch, an EllBatchStreamed or an
+        EllStableBatchStreamed).  Returns
         (x_best [B][n] with NaN rows where there is none, has_best [B], niter [B], gamma [B], status [B])."""
         gamma = np.array(np.broadcast_to(np.asarray(gamma, dtype=np.float64), (self.B,)))
         x_best = np.full((self.B, self.n), np.nan)

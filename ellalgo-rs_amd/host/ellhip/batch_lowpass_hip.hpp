@@ -3,7 +3,8 @@
 //     for b in 0..B { cutting_plane_optim(&mut omega[b], &mut space[b], &mut gamma[b], &options) }
 // with omega[b] a LowpassOracle (src/oracles/lowpass_oracle.rs:7-151) of its own band edges and ripple limits and
 // space[b] the b-th ellipsoid of an EllBatchHip.  Bit-identical to the CPU arithmetic.  BatchLowpassHip::streamed
-// (include/ellhip_batch_lowpass_streamed.h) takes filter lengths up to 1024 and solves on an EllBatchStreamedHip.
+// (include/ellhip_batch_lowpass_streamed.h) takes filter lengths up to 1024 and solves on an EllBatchStreamedHip or, through
+// include/ellhip_batch_lowpass_streamed_stable.h, on an EllStableBatchStreamedHip.
 #pragma once
 
 #include <cstdint>
@@ -11,7 +12,7 @@
 #include <utility>
 #include <vector>
 
-#include "../../../include/ellhip_batch_lowpass_streamed.h"
+#include "../../../include/ellhip_batch_lowpass_streamed_stable.h"
 #include "../../../include/ellhip_batch_stable_loops.h"
 #include "ell_batch_hip.hpp"
 
@@ -41,7 +42,7 @@ class BatchLowpassHip {
     // spectrum: empty = computed as the reference does; else the shared table, row-major 15 ndim x ndim
     BatchLowpassHip(std::size_t ndim, const std::vector<LowpassSpec>& specs, const Arr& spectrum = Arr(), int device = -1)
         : BatchLowpassHip(ndim, specs, spectrum, device, false) {}
-    // the same problems for ndim up to 1024: optim / feas then take an EllBatchStreamedHip
+    // the same problems for ndim up to 1024: optim / feas then take an EllBatchStreamedHip or an EllStableBatchStreamedHip
     static BatchLowpassHip streamed(std::size_t ndim, const std::vector<LowpassSpec>& specs, const Arr& spectrum = Arr(),
                                     int device = -1) {
         return BatchLowpassHip(ndim, specs, spectrum, device, true);
@@ -85,8 +86,9 @@ class BatchLowpassHip {
         return r;
     }
     // cutting_plane_optim (src/cutting_plane.rs:286-313) for every problem; gamma has B entries and is updated
-    // (spaces: an EllBatchHip, an EllStableBatchHip through include/ellhip_batch_stable_loops.h, or an EllBatchStreamedHip
-    // through include/ellhip_batch_lowpass_streamed.h)
+    // (spaces: an EllBatchHip, an EllStableBatchHip through include/ellhip_batch_stable_loops.h, an EllBatchStreamedHip
+    // through include/ellhip_batch_lowpass_streamed.h, or an EllStableBatchStreamedHip through
+    // include/ellhip_batch_lowpass_streamed_stable.h)
     template <int VARIANT, bool STREAMED>
     BatchLowpassResult optim(BatchHip<VARIANT, STREAMED>& spaces, Arr& gamma, const Options& options) {
         constexpr bool stable = VARIANT == ELLHIP_SPACE_ELL_STABLE;
@@ -94,12 +96,16 @@ class BatchLowpassHip {
         Arr x(B_ * n_);
         std::vector<int32_t> has(B_), status(B_);
         std::vector<int64_t> niter(B_);
-        const auto entry = STREAMED ? ellhip_batch_lowpass_optim_streamed
-                           : stable ? ellhip_batch_lowpass_optim_stable
-                                    : ellhip_batch_lowpass_optim;
+        const auto entry = STREAMED && stable ? ellhip_batch_lowpass_optim_streamed_stable
+                           : STREAMED         ? ellhip_batch_lowpass_optim_streamed
+                           : stable           ? ellhip_batch_lowpass_optim_stable
+                                              : ellhip_batch_lowpass_optim;
         check(entry(spaces.handle(), h_, gamma.data(), (int64_t)options.max_iters, options.tolerance, x.data(), has.data(),
                     niter.data(), status.data()),
-              STREAMED ? "ellhip_batch_lowpass_optim_streamed" : stable ? "ellhip_batch_lowpass_optim_stable" : "ellhip_batch_lowpass_optim");
+              STREAMED && stable ? "ellhip_batch_lowpass_optim_streamed_stable"
+              : STREAMED         ? "ellhip_batch_lowpass_optim_streamed"
+              : stable           ? "ellhip_batch_lowpass_optim_stable"
+                                 : "ellhip_batch_lowpass_optim");
         return result(x, has, niter, status);
     }
     // cutting_plane_feas (:205-227) for every problem
@@ -109,12 +115,16 @@ class BatchLowpassHip {
         Arr x(B_ * n_);
         std::vector<int32_t> has(B_), status(B_);
         std::vector<int64_t> niter(B_);
-        const auto entry = STREAMED ? ellhip_batch_lowpass_feas_streamed
-                           : stable ? ellhip_batch_lowpass_feas_stable
-                                    : ellhip_batch_lowpass_feas;
+        const auto entry = STREAMED && stable ? ellhip_batch_lowpass_feas_streamed_stable
+                           : STREAMED         ? ellhip_batch_lowpass_feas_streamed
+                           : stable           ? ellhip_batch_lowpass_feas_stable
+                                              : ellhip_batch_lowpass_feas;
         check(entry(spaces.handle(), h_, (int64_t)options.max_iters, options.tolerance, x.data(), has.data(), niter.data(),
                     status.data()),
-              STREAMED ? "ellhip_batch_lowpass_feas_streamed" : stable ? "ellhip_batch_lowpass_feas_stable" : "ellhip_batch_lowpass_feas");
+              STREAMED && stable ? "ellhip_batch_lowpass_feas_streamed_stable"
+              : STREAMED         ? "ellhip_batch_lowpass_feas_streamed"
+              : stable           ? "ellhip_batch_lowpass_feas_stable"
+                                 : "ellhip_batch_lowpass_feas");
         return result(x, has, niter, status);
     }
     std::vector<Fields> fields() const {

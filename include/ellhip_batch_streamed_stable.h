@@ -15,8 +15,10 @@
  * as the reference would hold it (diagonal = D, strict upper = the factor, strict lower = scratch).  Inside the handle the
  * scratch triangle is kept in another order; the constructors and ellhip_batch_get_mq convert, nothing else shows it.
  *
- * Every batched cutting-plane loop refuses such a handle with ELLHIP_E_INVALID and leaves it untouched: the loops of
- * ellhip_batch_{lmi,lowpass,svm}.h, their _stable forms and ellhip_batch_lowpass_{optim,feas}_streamed.
+ * Of the batched cutting-plane loops the low-pass one runs on such a handle, through entry points of its own
+ * (ellhip_batch_lowpass_streamed_stable.h).  Every other loop entry point refuses it with ELLHIP_E_INVALID and leaves it
+ * untouched: the loops of ellhip_batch_{lmi,lowpass,svm}.h, their _stable forms and
+ * ellhip_batch_lowpass_{optim,feas}_streamed.
  *
  * Traffic per ellipsoid, what the kernel moves: a cut reads the factor once for the forward solve (4 n^2 bytes) and writes
  * the scratch triangle (4 n^2); a successful cut reads the scratch triangle twice more (8 n^2) and reads and writes the

@@ -1,7 +1,7 @@
 """The batched device-resident low-pass design loop on a streamed batch handle (include/ellhip_batch_lowpass_streamed.h)
 against the two other ways to run the same sweep at filter lengths past 128: one JSON line per shape.
 
-  python tools/batch_lowpass_streamed_bench.py [--shapes 129:1536:300,256:1536:200,512:768:150,1024:256:100]
+  python tools/batch_lowpass_streamed_bench.py [--space ell|stable] [--shapes 129:1536:300,256:1536:200,512:768:150,1024:256:100]
                                                [--reps 3] [--warmup 1] [--host-b 16] [--chunks 256] [--out FILE]
 
 A shape is n:B:max_iters.  Workload (tests/batch_lowpass_reference.py: family): B specifications of one filter length n,
@@ -24,7 +24,14 @@ result (every chunk) and the host-driven result must equal the CPU's bit for bit
 
 rows_per_iter: row . x products per oracle call, from the CPU oracle's counter, averaged over the six members.  Byte model
 per instance and round: 16 n^2 (+ 8 n^2 once per launch) of matrix, 8 n per visited row of the transposed table, 8 n for the
-gradient row; model_bytes_per_round and the bandwidth the measured device rate implies under it are printed."""
+gradient row; model_bytes_per_round and the bandwidth the measured device rate implies under it are printed.
+
+--space stable runs the same three forms on EllStable spaces (include/ellhip_batch_lowpass_streamed_stable.h, DESIGN section
+9.9): the device form is ellhip_batch_lowpass_optim_streamed_stable on an EllStableBatchStreamed, the CPU loop runs over
+OracleEllStable::new_with_scalar(40, 0), the host-driven form calls ellhip_batch_update on a streamed EllStable handle.  On
+these spaces the family ends with NoSoln after about 1.1 n ... 1.7 n rounds, so the default shapes are
+129:1536:50000,256:512:50000 (complete runs) and 512:512:300,1024:512:90 (cut off).  Byte model per instance and round:
+24 n^2 of packed buffer (no fusion, nothing once per launch), the oracle's bytes as above."""
 from __future__ import annotations
 
 import argparse
@@ -49,8 +56,19 @@ def rounds_of(niter, max_iters):
     return int(np.sum(np.where(niter < max_iters, niter + 1, niter)))
 
 
+STABLE = False  # --space stable
+
+
 def new_spaces(pkg, n, B):
-    return pkg.EllBatchStreamed.new_with_scalar(np.full(B, KAPPA), np.zeros((B, n)), device=0)
+    cls = pkg.EllStableBatchStreamed if STABLE else pkg.EllBatchStreamed
+    return cls.new_with_scalar(np.full(B, KAPPA), np.zeros((B, n)), device=0)
+
+
+def fresh(ref, n, consts):
+    """a CPU oracle and its CPU space"""
+    if not STABLE:
+        return ref.fresh(n, consts)
+    return ref.O.OracleLowpass(n, *consts), ref.O.OracleEllStable.new_with_scalar(KAPPA, np.zeros(n))
 
 
 def device_run(pkg, prob, gamma0, max_iters, chunk):
@@ -65,7 +83,7 @@ def device_run(pkg, prob, gamma0, max_iters, chunk):
 
 def cpu_run(ref, n, max_iters):
     """the six distinct members, one thread -> (records, seconds)"""
-    pairs = [ref.fresh(n, ref.family(s)) for s in range(6)]
+    pairs = [fresh(ref, n, ref.family(s)) for s in range(6)]
     recs = []
     t0 = time.perf_counter()
     for s, (omega, space) in enumerate(pairs):
@@ -78,7 +96,7 @@ def cpu_rows(ref, n, recs, max_iters):
     """the rows the walk visits, call by call, on a second oracle per member -> rows per oracle call"""
     rows = calls = 0
     for s, r in enumerate(recs):
-        omega, space = ref.fresh(n, ref.family(s))
+        omega, space = fresh(ref, n, ref.family(s))
         gamma = ref.family(s)[4]
         for _ in range(rounds_of([r["niter"]], max_iters)):
             (g, (b0, b1)), shrunk, gamma = omega.assess_optim(np.array(space.xc), gamma)
@@ -165,7 +183,7 @@ def bench(pkg, ref, n, B, max_iters, reps, warmup, host_b, chunks):
     rows = cpu_rows(ref, n, recs, max_iters)
     cpu_rate = {k: cpu_rounds / v for k, v in summary(cpu_t).items() if k != "reps"}
     host_rate = {k: host_rounds / v for k, v in summary(host_t).items() if k != "reps"}
-    out = {"bench": "batch_lowpass_streamed", "n": n, "B": B, "max_iters": max_iters, "rounds": rounds,
+    out = {"bench": "batch_lowpass_streamed_stable" if STABLE else "batch_lowpass_streamed", "n": n, "B": B, "max_iters": max_iters, "rounds": rounds,
            "niter_min": int(got["niter"].min()), "niter_max": int(got["niter"].max()), "rows_per_iter": rows,
            "cpu_s_six_members": summary(cpu_t), "cpu_iters_per_s": cpu_rate["median"],
            "host_B": hb, "host_s": summary(host_t), "host_iters_per_s": host_rate["median"], "device": {}}
@@ -174,7 +192,7 @@ def bench(pkg, ref, n, B, max_iters, reps, warmup, host_b, chunks):
         s = summary(dev_t[c])
         rate = rounds / s["median"]
         launches = max(1, -(-max_iters // c))
-        matrix = 16.0 * n * n + 8.0 * n * n * launches / max_iters
+        matrix = 24.0 * n * n if STABLE else 16.0 * n * n + 8.0 * n * n * launches / max_iters
         model = matrix + 8.0 * n * rows + 8.0 * n
         out["device"][str(c)] = {
             "s": s, "iters_per_s": rate, "solves_per_s": B / s["median"], "over_cpu_one_thread": rate / cpu_rate["median"],
@@ -186,13 +204,21 @@ def bench(pkg, ref, n, B, max_iters, reps, warmup, host_b, chunks):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--shapes", default="129:1536:300,256:1536:200,512:768:150,1024:256:100")
+    ap.add_argument("--space", choices=("ell", "stable"), default="ell")
+    ap.add_argument("--shapes", default=None,
+                    help="default 129:1536:300,256:1536:200,512:768:150,1024:256:100 "
+                         "(--space stable: 129:1536:50000,256:512:50000,512:512:300,1024:512:90)")
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--host-b", type=int, default=16)
     ap.add_argument("--chunks", default="256")
     ap.add_argument("--out", default=None, help="append the JSON lines to this file as well")
     args = ap.parse_args()
+    global STABLE
+    STABLE = args.space == "stable"
+    if args.shapes is None:
+        args.shapes = ("129:1536:50000,256:512:50000,512:512:300,1024:512:90" if STABLE
+                       else "129:1536:300,256:1536:200,512:768:150,1024:256:100")
     import ellalgo_rs_amd as pkg
     import batch_lowpass_reference as ref
     if pkg.capi.load().ellhip_device_count() <= 0:
