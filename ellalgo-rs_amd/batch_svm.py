@@ -1,7 +1,8 @@
 """Python mirror of the batched device-resident SVM cutting-plane loop (include/ellhip_batch_svm.h): B independent
 `SvmOracle`s (src/oracles/svm_oracle.rs) of one shape (m samples, nfeat <= 127 features), each with its own labels and its
 own ellipsoid of an `EllBatch` (dimension nfeat + 1), over one shared table or one table per problem; solved by one kernel
-per chunk of iterations.  Bit-identical to the CPU arithmetic."""
+per chunk of iterations.  `BatchSvmProblem.streamed` (include/ellhip_batch_svm_streamed.h) takes nfeat up to 1023 and solves
+on an `EllBatchStreamed` or an `EllStableBatchStreamed`.  Bit-identical to the CPU arithmetic."""
 from __future__ import annotations
 
 import ctypes as C
@@ -12,8 +13,16 @@ from . import capi
 from .ell import _f64, _p
 
 
+def _loop_entry(batch, name: str) -> str:
+    """the `_streamed` entry point for an EllBatchStreamed, `_streamed_stable` for an EllStableBatchStreamed
+    (include/ellhip_batch_svm_streamed.h), else what capi.batch_loop_entry chooses"""
+    if not getattr(batch, "is_streamed", False):
+        return capi.batch_loop_entry(batch, name)
+    return name + ("_streamed_stable" if batch.variant == capi.SPACE_ELL_STABLE else "_streamed")
+
+
 class BatchSvmProblem:
-    def __init__(self, data, labels, *, shared=None, device: int = -1):
+    def __init__(self, data, labels, *, shared=None, device: int = -1, _create: str = "ellhip_batch_svm_create"):
         """data: m x nfeat (one table for every problem) or B x m x nfeat; labels: B x m integers (stored as int32,
         converted `as f64`).  shared: None = inferred from data.ndim."""
         self._lib = capi.load()
@@ -28,10 +37,16 @@ class BatchSvmProblem:
         if data.shape[:-1] != ((m,) if shared else (B, m)):
             raise ValueError(f"data has shape {data.shape}, labels {lab.shape}")
         h = C.c_void_p()
-        capi.check(self._lib.ellhip_batch_svm_create(C.byref(h), B, m, nfeat, _p(data), int(bool(shared)), _p(lab),
-                                                     int(device)), "ellhip_batch_svm_create")
+        capi.check(getattr(self._lib, _create)(C.byref(h), B, m, nfeat, _p(data), int(bool(shared)), _p(lab), int(device)),
+                   _create)
         self._h = h
         self.B, self.m, self.nfeat, self.n, self.shared = int(B), int(m), int(nfeat), int(nfeat) + 1, bool(shared)
+
+    @classmethod
+    def streamed(cls, data, labels, *, shared=None, device: int = -1):
+        """The same problems for 1 <= nfeat <= 1023 (include/ellhip_batch_svm_streamed.h): `optim` then takes an
+        `EllBatchStreamed` or an `EllStableBatchStreamed` of dimension nfeat + 1."""
+        return cls(data, labels, shared=shared, device=device, _create="ellhip_batch_svm_create_streamed")
 
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None
@@ -67,14 +82,15 @@ class BatchSvmProblem:
         return idx, val
 
     def optim(self, batch, gamma, max_iters: int, tol: float):
-        """cutting_plane_optim per problem on `batch` (an EllBatch or an EllStableBatch of dimension nfeat + 1).  Returns
+        """cutting_plane_optim per problem on `batch` (an EllBatch, an EllStableBatch, an EllBatchStreamed or an
+        EllStableBatchStreamed of dimension nfeat + 1).  Returns
         (x_best [B][n] with NaN rows where there is none, has_best [B], niter [B], gamma [B], status [B])."""
         gamma = np.array(np.broadcast_to(np.asarray(gamma, dtype=np.float64), (self.B,)))
         x_best = np.full((self.B, self.n), np.nan)
         has = np.empty(self.B, dtype=np.int32)
         niter = np.empty(self.B, dtype=np.int64)
         status = np.empty(self.B, dtype=np.int32)
-        entry = capi.batch_loop_entry(batch, "ellhip_batch_svm_optim")
+        entry = _loop_entry(batch, "ellhip_batch_svm_optim")
         capi.check(getattr(self._lib, entry)(batch._h, self._h, _p(gamma), int(max_iters), float(tol), _p(x_best), _p(has),
                                              _p(niter), _p(status)), entry)
         return x_best, has, niter, gamma, status

@@ -117,6 +117,11 @@ BATCH_LOWPASS_STREAMED_STABLE_EXPORTS = [
     "ellhip_batch_lowpass_optim_streamed_stable", "ellhip_batch_lowpass_feas_streamed_stable",
 ]
 
+# every symbol include/ellhip_batch_svm_streamed.h declares (kept apart from EXPORTS, like SVM_EXPORTS)
+BATCH_SVM_STREAMED_EXPORTS = [
+    "ellhip_batch_svm_create_streamed", "ellhip_batch_svm_optim_streamed", "ellhip_batch_svm_optim_streamed_stable",
+]
+
 
 class EllHipError(RuntimeError):
     pass
@@ -374,10 +379,14 @@ def load():
         # include/ellhip_batch_lowpass_streamed_stable.h (each as its counterpart in ellhip_batch_lowpass_streamed.h)
         "ellhip_batch_lowpass_optim_streamed_stable": (i32, [vp, vp, vp, i64, dbl, vp, vp, vp, vp]),
         "ellhip_batch_lowpass_feas_streamed_stable": (i32, [vp, vp, i64, dbl, vp, vp, vp, vp]),
+        # include/ellhip_batch_svm_streamed.h (each as its counterpart in ellhip_batch_svm.h)
+        "ellhip_batch_svm_create_streamed": (i32, [C.POINTER(vp), i64, i64, i64, vp, i32, vp, i32]),
+        "ellhip_batch_svm_optim_streamed": (i32, [vp, vp, vp, i64, dbl, vp, vp, vp, vp]),
+        "ellhip_batch_svm_optim_streamed_stable": (i32, [vp, vp, vp, i64, dbl, vp, vp, vp, vp]),
     }
     for name in (EXPORTS + SVM_EXPORTS + BATCH_LMI_EXPORTS + BATCH_LOWPASS_EXPORTS + BATCH_SVM_EXPORTS + LMI_LOOP_EXPORTS +
                  BATCH_STABLE_LOOP_EXPORTS + BATCH_STREAMED_EXPORTS + BATCH_LOWPASS_STREAMED_EXPORTS +
-                 BATCH_STREAMED_STABLE_EXPORTS + BATCH_LOWPASS_STREAMED_STABLE_EXPORTS):
+                 BATCH_STREAMED_STABLE_EXPORTS + BATCH_LOWPASS_STREAMED_STABLE_EXPORTS + BATCH_SVM_STREAMED_EXPORTS):
         fn = getattr(L, name)  # AttributeError if the library does not export it
         fn.restype, fn.argtypes = sig[name]
     _lib = L

@@ -49,19 +49,23 @@ int batch_svm_assess(ellhip_batch_svm* o, const double* x, int keep_last, double
             return fail(e == hipErrorOutOfMemory ? ELLHIP_E_NOMEM : ELLHIP_E_HIP, "batched svm margins allocation", e);
     }
     const size_t per = batch_svm_lds_doubles(o->n) + n;
+    // past the LDS engine's n (batch_row_shape has no instance per workgroup to offer): one instance per workgroup, n threads
+    // rounded up to whole waves, as the streamed engine shapes its own
+    const bool wide = o->n > BATCH_NMAX;
     const BatchRowShape sh = batch_row_shape(o->n, per);
-    const int T = sh.T, epw = sh.epw;
-    const size_t lds = (size_t)epw * per * sizeof(double);  // at most 64 * 15 * 8 bytes
+    const int T = wide ? (o->n + 63) / 64 * 64 : sh.T, epw = wide ? 1 : sh.epw;
+    const size_t lds = (size_t)epw * per * sizeof(double);  // at most 64 * 15 * 8 bytes, or 16.1 KiB at n = 1024
     const unsigned grid = (unsigned)((o->B + epw - 1) / epw);
     const BatchSvmOracle::Args A = batch_svm_args(o);
     double* d_beta = o->d_beta;
     double* d_gamma = o->d_beta + B;
     HIPCHK(hipMemcpy(o->d_x, x, B * n * sizeof(double), hipMemcpyHostToDevice));
 #define BATCH_SVM_ASSESS(TT)                                                                                           \
-    hipLaunchKernelGGL(k_batch_svm_assess<TT>, dim3(grid), dim3(TT), lds, o->loop.stream, o->B, o->n, epw, keep_last,  \
+    hipLaunchKernelGGL(k_batch_svm_assess<TT>, dim3(grid), dim3(T), lds, o->loop.stream, o->B, o->n, epw, keep_last,   \
                        A, (const double*)o->d_x, d_gamma, o->d_grad, d_beta,                                           \
                        margins_out ? o->d_margins : (double*)nullptr)
-    if (T == 128) BATCH_SVM_ASSESS(128);
+    if (wide) BATCH_SVM_ASSESS(1024);  // (the template argument bounds the block; the block is T threads)
+    else if (T == 128) BATCH_SVM_ASSESS(128);
     else BATCH_SVM_ASSESS(256);
 #undef BATCH_SVM_ASSESS
     HIPCHK(hipGetLastError());
@@ -73,17 +77,15 @@ int batch_svm_assess(ellhip_batch_svm* o, const double* x, int keep_last, double
     return 0;
 }
 
-}  // namespace
-
-extern "C" {
-
-int ellhip_batch_svm_create(ellhip_batch_svm** out, int64_t B, int64_t m, int64_t nfeat, const double* data,
-                            int32_t shared_data, const int32_t* labels, int device) {
+// nfeat_max: 127 for the LDS engine's constructor, 1023 for the streamed one (batch_svm_streamed_capi.inc.hpp)
+int batch_svm_create(ellhip_batch_svm** out, int64_t B, int64_t m, int64_t nfeat, const double* data, int32_t shared_data,
+                     const int32_t* labels, int device, int nfeat_max) {
     if (!out) return fail(ELLHIP_E_INVALID, "out is NULL");
     *out = nullptr;
     if (B < 1 || B > (1 << 24)) return fail(ELLHIP_E_INVALID, "batched svm: need 1 <= B <= 2^24");
     if (m < 1 || m > (1 << 24)) return fail(ELLHIP_E_INVALID, "batched svm: need 1 <= m <= 2^24 samples");
-    if (nfeat < 1 || nfeat > BATCH_NMAX - 1) return fail(ELLHIP_E_INVALID, "batched svm: need 1 <= nfeat <= 127 features");
+    if (nfeat < 1 || nfeat > nfeat_max)
+        return fail(ELLHIP_E_INVALID, ("batched svm: need 1 <= nfeat <= " + std::to_string(nfeat_max) + " features").c_str());
     if (!data || !labels) return fail(ELLHIP_E_INVALID, "NULL argument");
     const int ndev = ellhip_device_count();
     if (ndev <= 0) return fail(ELLHIP_E_NODEVICE, "no HIP device: the batched svm loop has no CPU path");
@@ -149,6 +151,15 @@ int ellhip_batch_svm_create(ellhip_batch_svm** out, int64_t B, int64_t m, int64_
     if (e != hipSuccess) return bail(fail(ELLHIP_E_HIP, "batched svm table upload", e));
     *out = o;
     return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ellhip_batch_svm_create(ellhip_batch_svm** out, int64_t B, int64_t m, int64_t nfeat, const double* data,
+                            int32_t shared_data, const int32_t* labels, int device) {
+    return batch_svm_create(out, B, m, nfeat, data, shared_data, labels, device, BATCH_NMAX - 1);
 }
 
 void ellhip_batch_svm_destroy(ellhip_batch_svm* o) {

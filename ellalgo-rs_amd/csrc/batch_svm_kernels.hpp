@@ -25,6 +25,12 @@
 //
 // Barriers are workgroup-wide; instances that take no part are masked off.  Every loop is bounded by ceil(m / n), nfeat
 // and n; no thread waits on another workgroup.
+//
+// Nothing here is tied to the number of instances in a workgroup or to n <= 128: the streamed loops
+// (k_batch_streamed_loop<BatchSvmOracle>, k_batch_streamed_loop_stable<BatchSvmOracle>; batch_svm_streamed_capi.inc.hpp,
+// DESIGN section 9.10) take this policy unchanged with one instance per workgroup of n rounded up to 64 threads, n <= 1024.
+// Bounded for 1024 threads (128 VGPRs a wave) they take 92 and 102 VGPRs and no scratch with BATCH_SVM_UNROLL = 8, so the
+// unroll is the same for every instantiation.
 #pragma once
 
 #include <climits>
@@ -179,6 +185,10 @@ struct BatchSvmOracle {
 
 // One assess_optim per instance at x[B][n]: the same device function, without an ellipsoid.  keep_last: record the scan in
 // A.min_idx / A.min_val (the margins entry point looks without touching the oracle's state).  margins: [B][m] or null.
+// Two launch shapes: epw instances packed into T = 128 or 256 threads (n <= 128), or the wide one past it -- epw = 1, one
+// workgroup per instance, blockDim.x = n rounded up to 64 (T = 1024 only bounds the block); threads tid >= n belong to no
+// instance (e = 1 >= epw), are inactive in the oracle and take part in its barriers.  LDS: epw * (batch_svm_lds_doubles(n) +
+// n) doubles.  Every loop is bounded by ceil(m / n), nfeat and n; no thread waits on another workgroup or on a memory word.
 template <int T>
 __global__ __launch_bounds__(T) void k_batch_svm_assess(long long B, int n, int epw, int keep_last, BatchSvmOracle::Args A,
                                                         const double* __restrict__ x, double* __restrict__ gamma_out,

@@ -3,6 +3,8 @@
 //     for b in 0..B { cutting_plane_optim(&mut omega[b], &mut space[b], &mut gamma[b], &options) }
 // with omega[b] a SvmOracle (src/oracles/svm_oracle.rs:4-58) over its own labels and its own or a shared table, and
 // space[b] the b-th ellipsoid of an EllBatchHip of dimension nfeat + 1.  Bit-identical to the CPU arithmetic.
+// BatchSvmHip::streamed (include/ellhip_batch_svm_streamed.h) takes up to 1023 features and solves on an EllBatchStreamedHip
+// or an EllStableBatchStreamedHip.
 #pragma once
 
 #include <cstdint>
@@ -11,6 +13,7 @@
 #include <vector>
 
 #include "../../../include/ellhip_batch_stable_loops.h"
+#include "../../../include/ellhip_batch_svm_streamed.h"
 #include "ell_batch_hip.hpp"
 
 namespace ellhip {
@@ -33,12 +36,11 @@ class BatchSvmHip {
     // data: row-major m x nfeat when `shared` (one table for every problem), else B x m x nfeat; labels: B x m
     BatchSvmHip(std::size_t B, std::size_t m, std::size_t nfeat, const Arr& data, bool shared,
                 const std::vector<int32_t>& labels, int device = -1)
-        : B_(B), m_(m), n_(nfeat + 1) {
-        if (data.size() != (shared ? 1 : B) * m * nfeat) throw Error(ELLHIP_E_INVALID, "data must be [B] x m x nfeat");
-        if (labels.size() != B * m) throw Error(ELLHIP_E_INVALID, "labels must be B x m");
-        check(ellhip_batch_svm_create(&h_, (int64_t)B, (int64_t)m, (int64_t)nfeat, data.data(), shared ? 1 : 0,
-                                      labels.data(), device),
-              "ellhip_batch_svm_create");
+        : BatchSvmHip(B, m, nfeat, data, shared, labels, device, false) {}
+    // the same problems for nfeat up to 1023: optim then takes an EllBatchStreamedHip or an EllStableBatchStreamedHip
+    static BatchSvmHip streamed(std::size_t B, std::size_t m, std::size_t nfeat, const Arr& data, bool shared,
+                                const std::vector<int32_t>& labels, int device = -1) {
+        return BatchSvmHip(B, m, nfeat, data, shared, labels, device, true);
     }
     BatchSvmHip(const BatchSvmHip&) = delete;
     BatchSvmHip& operator=(const BatchSvmHip&) = delete;
@@ -78,18 +80,25 @@ class BatchSvmHip {
         return r;
     }
     // cutting_plane_optim (src/cutting_plane.rs:286-313) for every problem; gamma has B entries and is updated
-    // (spaces: an EllBatchHip, or an EllStableBatchHip through include/ellhip_batch_stable_loops.h)
-    template <int VARIANT>
-    BatchSvmResult optim(BatchHip<VARIANT>& spaces, Arr& gamma, const Options& options) {
+    // (spaces: an EllBatchHip, an EllStableBatchHip through include/ellhip_batch_stable_loops.h, or an EllBatchStreamedHip
+    // or an EllStableBatchStreamedHip through include/ellhip_batch_svm_streamed.h)
+    template <int VARIANT, bool STREAMED>
+    BatchSvmResult optim(BatchHip<VARIANT, STREAMED>& spaces, Arr& gamma, const Options& options) {
         constexpr bool stable = VARIANT == ELLHIP_SPACE_ELL_STABLE;
         if (gamma.size() != B_) throw Error(ELLHIP_E_INVALID, "gamma must have B entries");
         Arr x(B_ * n_);
         std::vector<int32_t> has(B_), status(B_);
         std::vector<int64_t> niter(B_);
-        check((stable ? ellhip_batch_svm_optim_stable : ellhip_batch_svm_optim)(
-                  spaces.handle(), h_, gamma.data(), (int64_t)options.max_iters, options.tolerance, x.data(), has.data(),
-                  niter.data(), status.data()),
-              stable ? "ellhip_batch_svm_optim_stable" : "ellhip_batch_svm_optim");
+        const auto entry = STREAMED && stable ? ellhip_batch_svm_optim_streamed_stable
+                           : STREAMED         ? ellhip_batch_svm_optim_streamed
+                           : stable           ? ellhip_batch_svm_optim_stable
+                                              : ellhip_batch_svm_optim;
+        check(entry(spaces.handle(), h_, gamma.data(), (int64_t)options.max_iters, options.tolerance, x.data(), has.data(),
+                    niter.data(), status.data()),
+              STREAMED && stable ? "ellhip_batch_svm_optim_streamed_stable"
+              : STREAMED         ? "ellhip_batch_svm_optim_streamed"
+              : stable           ? "ellhip_batch_svm_optim_stable"
+                                 : "ellhip_batch_svm_optim");
         BatchSvmResult r;
         for (std::size_t b = 0; b < B_; ++b) {
             if (has[b]) r.x_best.emplace_back(Arr(x.begin() + b * n_, x.begin() + (b + 1) * n_));
@@ -103,6 +112,15 @@ class BatchSvmHip {
     ellhip_batch_svm* handle() { return h_; }
 
   private:
+    BatchSvmHip(std::size_t B, std::size_t m, std::size_t nfeat, const Arr& data, bool shared,
+                const std::vector<int32_t>& labels, int device, bool streamed)
+        : B_(B), m_(m), n_(nfeat + 1) {
+        if (data.size() != (shared ? 1 : B) * m * nfeat) throw Error(ELLHIP_E_INVALID, "data must be [B] x m x nfeat");
+        if (labels.size() != B * m) throw Error(ELLHIP_E_INVALID, "labels must be B x m");
+        check((streamed ? ellhip_batch_svm_create_streamed : ellhip_batch_svm_create)(
+                  &h_, (int64_t)B, (int64_t)m, (int64_t)nfeat, data.data(), shared ? 1 : 0, labels.data(), device),
+              streamed ? "ellhip_batch_svm_create_streamed" : "ellhip_batch_svm_create");
+    }
     Arr flatten(const std::vector<Arr>& x) const {
         if (x.size() != B_) throw Error(ELLHIP_E_INVALID, "x must have B rows");
         Arr flat;

@@ -19,7 +19,8 @@
  * one sweeps of small problems.)  SvmOracle implements OracleOptim only, so there is no `_feas` entry point.
  *
  * `EllStable` batch handles belong to ellhip_batch_stable_loops.h (ellhip_batch_svm_optim_stable): ellhip_batch_svm_optim
- * refuses them with ELLHIP_E_INVALID.
+ * refuses them with ELLHIP_E_INVALID.  Problems of up to 1023 features and streamed batch handles belong to
+ * ellhip_batch_svm_streamed.h; the entry points of this header keep refusing both.
  *
  * Memory: the table is kept feature-major on the device, nfeat x ld doubles per table with ld = m rounded up to 8; it is
  * transposed on the device at create from bounded slabs of the caller's rows.
