@@ -144,8 +144,8 @@ class EllStableBatch(_Batch):
 
 class EllBatchStreamed(EllBatch):
     """B `Ell` spaces of one dimension n <= 1024 with the matrices streamed from HBM (include/ellhip_batch_streamed.h):
-    the same calls and the same bits as `EllBatch`, past its n = 128.  Of the batched cutting-plane loops the low-pass and
-    the SVM ones run on it (`BatchLowpassProblem.streamed`, `BatchSvmProblem.streamed`); the LMI one refuses it."""
+    the same calls and the same bits as `EllBatch`, past its n = 128.  The batched cutting-plane loops run on it through
+    `BatchLowpassProblem.streamed`, `BatchSvmProblem.streamed` and `BatchLmiProblem.streamed`."""
     _create = "ellhip_batch_create_streamed"
     _from_space = "ellhip_batch_streamed_from_space"
 
@@ -159,9 +159,9 @@ class EllBatchStreamed(EllBatch):
 class EllStableBatchStreamed(EllStableBatch):
     """B `EllStable` spaces of one dimension n <= 1024 with the packed buffers streamed from HBM
     (include/ellhip_batch_streamed_stable.h): the same calls and the same bits as `EllStableBatch`, past its n = 128.
-    Of the batched cutting-plane loops the low-pass and the SVM ones run on it (`BatchLowpassProblem.streamed`,
-    include/ellhip_batch_lowpass_streamed_stable.h; `BatchSvmProblem.streamed`, include/ellhip_batch_svm_streamed.h); the
-    LMI one refuses it."""
+    The batched cutting-plane loops run on it (`BatchLowpassProblem.streamed`,
+    include/ellhip_batch_lowpass_streamed_stable.h; `BatchSvmProblem.streamed`, include/ellhip_batch_svm_streamed.h;
+    `BatchLmiProblem.streamed`, include/ellhip_batch_lmi_streamed.h)."""
     _create = "ellhip_batch_create_streamed_stable"
     _from_space = "ellhip_batch_streamed_stable_from_space"
     is_streamed = EllBatchStreamed.is_streamed

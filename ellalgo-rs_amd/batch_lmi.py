@@ -1,8 +1,9 @@
 """Python mirror of the batched device-resident LMI cutting-plane loop (include/ellhip_batch_lmi.h): B independent
 problems `min c'x  s.t.  B_j - sum_k x_k F_jk > 0` (or, without mat_b, `sum_k x_k F_jk > 0`), each with its own
 round-robin oracle (tests/lmi_tests.rs:142-171 generalised to J blocks) and its own ellipsoid of an `EllBatch` or an
-`EllStableBatch` (include/ellhip_batch_stable_loops.h), solved by one kernel per chunk of iterations.  Bit-identical to the
-CPU arithmetic."""
+`EllStableBatch` (include/ellhip_batch_stable_loops.h), solved by one kernel per chunk of iterations.
+`BatchLmiProblem.streamed` (include/ellhip_batch_lmi_streamed.h) takes n up to 1024, with one pencil per problem or one for
+all of them, and solves on an `EllBatchStreamed` or an `EllStableBatchStreamed`.  Bit-identical to the CPU arithmetic."""
 from __future__ import annotations
 
 import ctypes as C
@@ -13,16 +14,33 @@ from . import capi
 from .ell import _f64, _p
 
 
+def _loop_entry(spaces, name: str) -> str:
+    """the `_streamed` entry point for an EllBatchStreamed, `_streamed_stable` for an EllStableBatchStreamed
+    (include/ellhip_batch_lmi_streamed.h), else what capi.batch_loop_entry chooses"""
+    if not getattr(spaces, "is_streamed", False):
+        return capi.batch_loop_entry(spaces, name)
+    return name + ("_streamed_stable" if spaces.variant == capi.SPACE_ELL_STABLE else "_streamed")
+
+
 class BatchLmiProblem:
-    def __init__(self, mat_f, mat_b=None, c=None, *, device: int = -1):
+    def __init__(self, mat_f, mat_b=None, c=None, *, device: int = -1, _streamed: bool = False, _shared: bool = False):
         """mat_f: a list of J arrays [B][n][m_j][m_j]; mat_b: a list of J arrays [B][m_j][m_j] or None (LMI0 form);
         c: [B][n] or None (feasibility problem)."""
         self._lib = capi.load()
         mat_f = [np.ascontiguousarray(f, dtype=np.float64) for f in mat_f]
-        if not mat_f or any(f.ndim != 4 or f.shape[2] != f.shape[3] for f in mat_f):
+        if _shared:
+            if not mat_f or any(f.ndim != 3 or f.shape[1] != f.shape[2] for f in mat_f):
+                raise ValueError("a shared mat_f must be a list of [n][m][m] arrays")
+            if mat_b is None and c is None:
+                raise ValueError("a shared pencil needs mat_b or c to tell the number of problems")
+            B = len(mat_b[0]) if mat_b is not None else np.asarray(c).shape[0]
+            mat_f = [f[None] for f in mat_f]
+        elif not mat_f or any(f.ndim != 4 or f.shape[2] != f.shape[3] for f in mat_f):
             raise ValueError("mat_f must be a list of [B][n][m][m] arrays")
-        B, n = mat_f[0].shape[:2]
-        if any(f.shape[:2] != (B, n) for f in mat_f):
+        else:
+            B = mat_f[0].shape[0]
+        n = mat_f[0].shape[1]
+        if any(f.shape[:2] != (1 if _shared else B, n) for f in mat_f):
             raise ValueError("every block needs the same B and n")
         m = np.array([f.shape[2] for f in mat_f], dtype=np.int64)
         flat_f = np.concatenate([f.ravel() for f in mat_f])
@@ -34,11 +52,24 @@ class BatchLmiProblem:
             flat_b = np.concatenate([b.ravel() for b in mat_b])
         c = None if c is None else _f64(c, B * n)
         h = C.c_void_p()
-        capi.check(self._lib.ellhip_batch_lmi_create(C.byref(h), B, n, len(mat_f), _p(m), _p(flat_f), _p(flat_b), _p(c),
-                                                     device), "ellhip_batch_lmi_create")
+        if _streamed:
+            capi.check(self._lib.ellhip_batch_lmi_create_streamed(C.byref(h), B, n, len(mat_f), _p(m), _p(flat_f),
+                                                                  int(bool(_shared)), _p(flat_b), _p(c), device),
+                       "ellhip_batch_lmi_create_streamed")
+        else:
+            capi.check(self._lib.ellhip_batch_lmi_create(C.byref(h), B, n, len(mat_f), _p(m), _p(flat_f), _p(flat_b), _p(c),
+                                                         device), "ellhip_batch_lmi_create")
         self._h = h
         self.B, self.n, self.J = int(B), int(n), len(mat_f)
         self.has_c = c is not None
+        self.shared = bool(_shared)
+
+    @classmethod
+    def streamed(cls, mat_f, mat_b=None, c=None, *, shared: bool = False, device: int = -1):
+        """The same problems for 1 <= n <= 1024 (include/ellhip_batch_lmi_streamed.h): `optim` / `feas` then take an
+        `EllBatchStreamed` or an `EllStableBatchStreamed`.  shared: mat_f is a list of J arrays [n][m_j][m_j], one pencil
+        that every problem reads; mat_b and c stay per problem (one of them must be given: it tells B)."""
+        return cls(mat_f, mat_b, c, device=device, _streamed=True, _shared=shared)
 
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None
@@ -72,14 +103,15 @@ class BatchLmiProblem:
         return grad, beta, station, gamma
 
     def optim(self, spaces, gamma, max_iters: int, tol: float):
-        """cutting_plane_optim per problem on `spaces` (an EllBatch or an EllStableBatch).  Returns (x_best [B][n] with NaN rows where there
+        """cutting_plane_optim per problem on `spaces` (an EllBatch, an EllStableBatch, an EllBatchStreamed or an
+        EllStableBatchStreamed).  Returns (x_best [B][n] with NaN rows where there
         is none, has_best [B], niter [B], gamma [B], status [B])."""
         gamma = np.array(np.broadcast_to(np.asarray(gamma, dtype=np.float64), (self.B,)))
         x_best = np.full((self.B, self.n), np.nan)
         has = np.empty(self.B, dtype=np.int32)
         niter = np.empty(self.B, dtype=np.int64)
         status = np.empty(self.B, dtype=np.int32)
-        entry = capi.batch_loop_entry(spaces, "ellhip_batch_lmi_optim")
+        entry = _loop_entry(spaces, "ellhip_batch_lmi_optim")
         capi.check(getattr(self._lib, entry)(spaces._h, self._h, _p(gamma), int(max_iters), float(tol), _p(x_best), _p(has),
                                              _p(niter), _p(status)), entry)
         return x_best, has, niter, gamma, status
@@ -91,7 +123,7 @@ class BatchLmiProblem:
         ok = np.empty(self.B, dtype=np.int32)
         niter = np.empty(self.B, dtype=np.int64)
         status = np.empty(self.B, dtype=np.int32)
-        entry = capi.batch_loop_entry(spaces, "ellhip_batch_lmi_feas")
+        entry = _loop_entry(spaces, "ellhip_batch_lmi_feas")
         capi.check(getattr(self._lib, entry)(spaces._h, self._h, int(max_iters), float(tol), _p(x), _p(ok), _p(niter),
                                              _p(status)), entry)
         return x, ok, niter, status

@@ -122,6 +122,12 @@ BATCH_SVM_STREAMED_EXPORTS = [
     "ellhip_batch_svm_create_streamed", "ellhip_batch_svm_optim_streamed", "ellhip_batch_svm_optim_streamed_stable",
 ]
 
+# every symbol include/ellhip_batch_lmi_streamed.h declares (kept apart from EXPORTS, like SVM_EXPORTS)
+BATCH_LMI_STREAMED_EXPORTS = [
+    "ellhip_batch_lmi_create_streamed", "ellhip_batch_lmi_optim_streamed", "ellhip_batch_lmi_feas_streamed",
+    "ellhip_batch_lmi_optim_streamed_stable", "ellhip_batch_lmi_feas_streamed_stable",
+]
+
 
 class EllHipError(RuntimeError):
     pass
@@ -383,10 +389,17 @@ def load():
         "ellhip_batch_svm_create_streamed": (i32, [C.POINTER(vp), i64, i64, i64, vp, i32, vp, i32]),
         "ellhip_batch_svm_optim_streamed": (i32, [vp, vp, vp, i64, dbl, vp, vp, vp, vp]),
         "ellhip_batch_svm_optim_streamed_stable": (i32, [vp, vp, vp, i64, dbl, vp, vp, vp, vp]),
+        # include/ellhip_batch_lmi_streamed.h (the loops as their counterparts in ellhip_batch_lmi.h)
+        "ellhip_batch_lmi_create_streamed": (i32, [C.POINTER(vp), i64, i64, i64, vp, vp, i32, vp, vp, i32]),
+        "ellhip_batch_lmi_optim_streamed": (i32, [vp, vp, vp, i64, dbl, vp, vp, vp, vp]),
+        "ellhip_batch_lmi_feas_streamed": (i32, [vp, vp, i64, dbl, vp, vp, vp, vp]),
+        "ellhip_batch_lmi_optim_streamed_stable": (i32, [vp, vp, vp, i64, dbl, vp, vp, vp, vp]),
+        "ellhip_batch_lmi_feas_streamed_stable": (i32, [vp, vp, i64, dbl, vp, vp, vp, vp]),
     }
     for name in (EXPORTS + SVM_EXPORTS + BATCH_LMI_EXPORTS + BATCH_LOWPASS_EXPORTS + BATCH_SVM_EXPORTS + LMI_LOOP_EXPORTS +
                  BATCH_STABLE_LOOP_EXPORTS + BATCH_STREAMED_EXPORTS + BATCH_LOWPASS_STREAMED_EXPORTS +
-                 BATCH_STREAMED_STABLE_EXPORTS + BATCH_LOWPASS_STREAMED_STABLE_EXPORTS + BATCH_SVM_STREAMED_EXPORTS):
+                 BATCH_STREAMED_STABLE_EXPORTS + BATCH_LOWPASS_STREAMED_STABLE_EXPORTS + BATCH_SVM_STREAMED_EXPORTS +
+                 BATCH_LMI_STREAMED_EXPORTS):
         fn = getattr(L, name)  # AttributeError if the library does not export it
         fn.restype, fn.argtypes = sig[name]
     _lib = L

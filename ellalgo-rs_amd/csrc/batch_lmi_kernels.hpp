@@ -19,9 +19,24 @@
 // The pencil stays in HBM / L2, k fastest: F[inst][block][a][b][k], so the n threads of sym_quad read consecutive
 // doubles and a thread of F(x) walks n consecutive doubles; B[inst][block][a][b].
 //
+// Second layout for F(x) (handles of ellhip_batch_lmi_create_streamed; Args::tri non-null): beside the k-fastest pencil a
+// copy of the lower triangle only, element fastest: T[inst][block][k][t], t = a (a + 1) / 2 + b, b <= a.  Thread i then takes
+// the elements t = i, i + n, ... of the m (m + 1) / 2 and folds the same s -= T[k][t] * x[k], k ascending: the loads of a wave
+// are consecutive doubles, x[k] is a broadcast from LDS and no thread idles on b > a.  At n = 1024, m = 64 the k-fastest walk
+// makes every load instruction of a wave touch 64 cache lines 8 KiB apart, with half the threads idle in each of four passes.
+// The fold per element is the same sequence of operations, so the bits are the same.  Handles of ellhip_batch_lmi_create keep
+// tri null and run the code they always ran.
+//
 // Barriers are workgroup-wide, so the walk over stations runs in lockstep: every instance of the workgroup takes its
 // next station in the same step, and the column loop runs to the largest block size.  Every loop is bounded by J + 1, M
 // and n; no thread waits on another workgroup.
+//
+// Nothing here is tied to the number of instances in a workgroup or to n <= 128: the streamed loops
+// (k_batch_streamed_loop<BatchLmiOracle>, k_batch_streamed_loop_stable<BatchLmiOracle>; batch_lmi_streamed_capi.inc.hpp,
+// DESIGN section 9.11) take this policy unchanged with one instance per workgroup of n rounded up to 64 threads, n <= 1024.
+// Threads i >= n are not live, own no element, row or quadratic form, and reach every barrier and vote.  One pencil may
+// serve every instance (ellhip_batch_lmi_create_streamed, shared_f): Args::L.fstride is then 0, and load() is the only place
+// that applies it.
 #pragma once
 
 #include "batch_loop_kernels.hpp"
@@ -36,7 +51,9 @@ struct BatchLmiParams {
     int m[BATCH_LMI_JMAX];        // block sizes
     int foff[BATCH_LMI_JMAX];     // offset of block j inside an instance's pencil, in doubles
     int boff[BATCH_LMI_JMAX];     // offset of block j inside an instance's B matrices
-    int fstride;                  // n * sum m_j^2
+    int fstride;                  // n * sum m_j^2; 0 in the Args of a handle whose instances share one pencil
+    int toff[BATCH_LMI_JMAX];     // offset of block j inside an instance's triangle copy: n * sum_{j' < j} m_j' (m_j' + 1) / 2
+    int tstride;                  // n * sum m_j (m_j + 1) / 2; 0 when shared, like fstride
     int bstride;                  // sum m_j^2
     int mmax;                     // max m_j
     int pm;                       // LDS pitch of the factorisation (odd)
@@ -62,12 +79,13 @@ enum : int {
 
 // The oracle for the workgroup's instances, collectively (it contains barriers: every thread of the workgroup calls it).
 // live: this thread belongs to an instance that takes part.  x, cl: the instance's point and objective vector (LDS, n
-// each); fa: m x pm factorisation; wit; osc: scalars; gout: n doubles for the gradient.  F, Bm: this instance's pencil.
+// each); fa: m x pm factorisation; wit; osc: scalars; gout: n doubles for the gradient.  F, Bm: this instance's pencil;
+// Tr: its triangle copy, or null.
 // On return (after a barrier) osc[LO_STATION], osc[LO_BETA], osc[LO_GAMMA], osc[LO_IDX] and gout hold the answer.
 __device__ __forceinline__ void batch_lmi_oracle(const BatchLmiParams& L, const bool live, const int i, const int n,
                                                  const double* __restrict__ F, const double* __restrict__ Bm,
-                                                 const double* x, const double* cl, double* fa, double* wit, double* osc,
-                                                 double* gout) {
+                                                 const double* __restrict__ Tr, const double* x, const double* cl,
+                                                 double* fa, double* wit, double* osc, double* gout) {
     const int pm = L.pm;
     if (live && i == 0) {
         double f0 = 0.0;  //                                                tests/lmi_tests.rs:146
@@ -106,7 +124,28 @@ __device__ __forceinline__ void batch_lmi_oracle(const BatchLmiParams& L, const 
         }
         const int m = cur >= 0 ? L.m[cur] : 0;
         // ---- F(x), lower triangle                                        src/oracles/lmi_oracle.rs:28-34
-        if (cur >= 0) {
+        if (cur >= 0 && Tr) {  // the element-fastest triangle copy: t = a (a + 1) / 2 + b
+            const int nt = m * (m + 1) / 2;
+            const double* Tb = Tr + L.toff[cur];
+            const double* Bb = Bm + L.boff[cur];
+            for (int t = i; t < nt; t += n) {
+                // 8 t + 1 <= 16633 and sqrt is correctly rounded, so the floor is exact; the two steps only guard it
+                int a = (int)((sqrt(8.0 * (double)t + 1.0) - 1.0) * 0.5);
+                if (a * (a + 1) / 2 > t) a -= 1;
+                if ((a + 1) * (a + 2) / 2 <= t) a += 1;
+                const int b = t - a * (a + 1) / 2;
+                const double* f = Tb + t;
+                double s;
+                if (L.has_b) {
+                    s = Bb[a * m + b];
+                    for (int k = 0; k < n; ++k) s -= f[(size_t)k * nt] * x[k];
+                } else {
+                    s = 0.0;  //                                            src/oracles/lmi0_oracle.rs:18-24
+                    for (int k = 0; k < n; ++k) s += f[(size_t)k * nt] * x[k];
+                }
+                fa[a * pm + b] = s;
+            }
+        } else if (cur >= 0) {
             const double* Fb = F + L.foff[cur];
             const double* Bb = Bm + L.boff[cur];
             int a = i / m, b = i - a * m;
@@ -194,13 +233,14 @@ __device__ __forceinline__ void batch_lmi_oracle(const BatchLmiParams& L, const 
 struct BatchLmiOracle {
     struct Args {
         BatchLmiParams L;
-        const double* pencil;  // [B][block][a][b][k]
+        const double* pencil;  // [B][block][a][b][k]; [block][a][b][k] when L.fstride == 0
+        const double* tri;     // [B][block][k][t] ([block][k][t] when L.tstride == 0), or null: F(x) reads the pencil
         const double* matb;    // [B][block][a][b], or null
         const double* cvec;    // [B][n], or null
         int* idx;              // [B]
     };
     struct Regs {
-        const double *F, *Bm;  // this instance's pencil
+        const double *F, *Bm, *T;  // this instance's pencil and its triangle copy
     };
     struct Lds {
         double *x, *cl, *fa, *wit, *osc;
@@ -224,13 +264,14 @@ struct BatchLmiOracle {
         if (active && i == 0) d.osc[LO_IDX] = (double)A.idx[b];
         r.F = A.pencil + (active ? b : 0) * (long long)A.L.fstride;
         r.Bm = A.matb ? A.matb + (active ? b : 0) * (long long)A.L.bstride : nullptr;
+        r.T = A.tri ? A.tri + (active ? b : 0) * (long long)A.L.tstride : nullptr;
     }
     static __device__ __forceinline__ void assess(const Args& A, const BatchLoopRun&, bool live, int i, int n, double xci,
                                                   double* blk, Regs& r, double* g) {
         const Lds d = carve(A, n, blk);
         if (live) d.x[i] = xci;
         __syncthreads();
-        batch_lmi_oracle(A.L, live, i, n, r.F, r.Bm, d.x, d.cl, d.fa, d.wit, d.osc, g);
+        batch_lmi_oracle(A.L, live, i, n, r.F, r.Bm, r.T, d.x, d.cl, d.fa, d.wit, d.osc, g);
     }
     // every station passed: cutting_plane_optim shrinks (tests/lmi_tests.rs:170), cutting_plane_feas has its point
     static __device__ __forceinline__ BatchOutcome outcome(const Args& A, int feas, const double* osc) {
@@ -243,6 +284,11 @@ struct BatchLmiOracle {
 };
 
 // One oracle call per instance at x[B][n]: the same device function, without an ellipsoid.
+// Two launch shapes: epw instances packed into T = 128 or 256 threads (n <= 128), or the wide one past it -- epw = 1, one
+// workgroup per instance, blockDim.x = n rounded up to 64 (T = 1024 only bounds the block); threads tid >= n belong to no
+// instance (e = 1 >= epw), are inactive in the oracle and take part in its barriers.  LDS: epw * (batch_lmi_lds_doubles(n, M)
+// + n) doubles, 57.1 KiB at n = 1024, M = 64.  Every loop is bounded by J + 1, M and n; no thread waits on another workgroup
+// or on a memory word.
 template <int T>
 __global__ __launch_bounds__(T) void k_batch_lmi_assess(long long B, int n, int epw, BatchLmiOracle::Args A,
                                                         const double* __restrict__ x, double* __restrict__ gamma_io,
@@ -265,7 +311,7 @@ __global__ __launch_bounds__(T) void k_batch_lmi_assess(long long B, int n, int 
     }
     if (active && i == 0) d.osc[LO_GAMMA] = gamma_io[b];
     __syncthreads();
-    batch_lmi_oracle(A.L, active, i, n, r.F, r.Bm, d.x, d.cl, d.fa, d.wit, d.osc, g);
+    batch_lmi_oracle(A.L, active, i, n, r.F, r.Bm, r.T, d.x, d.cl, d.fa, d.wit, d.osc, g);
     if (active) grad_out[b * n + i] = g[i];
     if (active && i == 0) {
         gamma_io[b] = d.osc[LO_GAMMA];

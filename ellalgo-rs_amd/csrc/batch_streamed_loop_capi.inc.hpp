@@ -7,6 +7,25 @@
 
 namespace {
 
+// More than the default 64 KiB of dynamic LDS needs an opt-in per kernel and per device (batch_loop_allow_lds is the LDS
+// driver's): raised only, once per (oracle, device, kernel), with the high-water marks kept here.  slot 0:
+// k_batch_streamed_loop<Oracle>, slot 1: k_batch_streamed_loop_stable<Oracle>.  Launches within 64 KiB never come here, so
+// the low-pass and SVM loops (at most 48.2 and 48.1 KiB) run as they did.
+template <class Oracle>
+int batch_streamed_allow_lds(const void* kernel, int device, int slot, size_t bytes) {
+    constexpr int MAXDEV = 64;
+    static std::atomic<int> granted[MAXDEV][2];
+    if (bytes <= 64 * 1024) return 0;
+    const bool known = device >= 0 && device < MAXDEV;
+    if (known && (int)bytes <= granted[device][slot].load()) return 0;
+    HIPCHK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    if (known) {
+        int seen = granted[device][slot].load();
+        while (seen < (int)bytes && !granted[device][slot].compare_exchange_weak(seen, (int)bytes)) {}
+    }
+    return 0;
+}
+
 // The loops on the streamed engine: k_batch_streamed_loop over a streamed batch handle of Ell spaces.
 template <class Oracle>
 int batch_streamed_loop_run(ellhip_batch* s, BatchLoopBuffers& st, const typename Oracle::Args& A, const BatchLoopWords& w,
@@ -19,7 +38,8 @@ int batch_streamed_loop_run(ellhip_batch* s, BatchLoopBuffers& st, const typenam
         return fail(ELLHIP_E_INVALID, (what + ": spaces and oracle differ in B or n" + w.n_is).c_str());
     if (s->device != st.device) return fail(ELLHIP_E_INVALID, (what + ": spaces and oracle live on different devices").c_str());
     const size_t lds = batch_streamed_loop_lds_doubles<Oracle>(A, s->n) * sizeof(double);
-    if (lds > 64 * 1024) return fail(ELLHIP_E_INVALID, (what + ": this " + w.shape + " needs more LDS than the loop may use").c_str());
+    if (lds > BATCH_LOOP_LDS_MAX)
+        return fail(ELLHIP_E_INVALID, (what + ": this " + w.shape + " needs more LDS than a workgroup has").c_str());
     BatchStreamedParams P;
     P.B = s->B;
     P.n = s->n;
@@ -30,6 +50,9 @@ int batch_streamed_loop_run(ellhip_batch* s, BatchLoopBuffers& st, const typenam
     const BatchLoopState S = batch_loop_view(st);
     return batch_loop_drive(s, st, feas, gamma_inout, max_iters, tol, x_out, has_out, niter_out, status_out,
                             [&](const BatchLoopRun& R) {
+        if (const int rc = batch_streamed_allow_lds<Oracle>(reinterpret_cast<const void*>(&k_batch_streamed_loop<Oracle>),
+                                                            s->device, 0, lds))
+            return rc;
         hipLaunchKernelGGL(k_batch_streamed_loop<Oracle>, dim3((unsigned)s->B), dim3(s->T), lds, s->stream, P, R, s->d_Q, s->d_xc,
                            s->d_kappa, s->d_tsq, s->d_sym, S, A, calc);
         return 0;

@@ -23,7 +23,8 @@ int batch_streamed_stable_loop_run(ellhip_batch* s, BatchLoopBuffers& st, const 
         return fail(ELLHIP_E_INVALID, (what + ": spaces and oracle differ in B or n" + w.n_is).c_str());
     if (s->device != st.device) return fail(ELLHIP_E_INVALID, (what + ": spaces and oracle live on different devices").c_str());
     const size_t lds = batch_streamed_stable_loop_lds_doubles<Oracle>(A, s->n) * sizeof(double);
-    if (lds > 64 * 1024) return fail(ELLHIP_E_INVALID, (what + ": this " + w.shape + " needs more LDS than the loop may use").c_str());
+    if (lds > BATCH_LOOP_LDS_MAX)
+        return fail(ELLHIP_E_INVALID, (what + ": this " + w.shape + " needs more LDS than a workgroup has").c_str());
     BatchStreamedParams P;
     P.B = s->B;
     P.n = s->n;
@@ -34,6 +35,9 @@ int batch_streamed_stable_loop_run(ellhip_batch* s, BatchLoopBuffers& st, const 
     const BatchLoopState S = batch_loop_view(st);
     return batch_loop_drive(s, st, feas, gamma_inout, max_iters, tol, x_out, has_out, niter_out, status_out,
                             [&](const BatchLoopRun& R) {
+        if (const int rc = batch_streamed_allow_lds<Oracle>(
+                reinterpret_cast<const void*>(&k_batch_streamed_loop_stable<Oracle>), s->device, 1, lds))
+            return rc;
         hipLaunchKernelGGL(k_batch_streamed_loop_stable<Oracle>, dim3((unsigned)s->B), dim3(s->T), lds, s->stream, P, R, s->d_Q,
                            s->d_xc, s->d_kappa, s->d_tsq, S, A, calc);
         return 0;

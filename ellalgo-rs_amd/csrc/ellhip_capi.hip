@@ -2976,3 +2976,4 @@ int ellhip_profile_read(ellhip_space* s, double* ms_out, int64_t* count_out) {
 #include "batch_streamed_loop_capi.inc.hpp"
 #include "batch_streamed_stable_loop_capi.inc.hpp"
 #include "batch_svm_streamed_capi.inc.hpp"
+#include "batch_lmi_streamed_capi.inc.hpp"

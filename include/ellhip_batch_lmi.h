@@ -22,7 +22,8 @@
  * so iteration counts, x_best, gamma and the spaces afterwards are bit-identical to the CPU arithmetic.
  *
  * `EllStable` batch handles belong to ellhip_batch_stable_loops.h (ellhip_batch_lmi_optim_stable, _feas_stable): the loop
- * entry points here refuse them with ELLHIP_E_INVALID.
+ * entry points here refuse them with ELLHIP_E_INVALID.  Problems of up to 1024 variables and streamed batch handles belong
+ * to ellhip_batch_lmi_streamed.h; the entry points of this header keep refusing both.
  *
  * LDS: a workgroup holds `epw` problems, epw as the batch engine chooses it for n (ellhip_batch.h).  With
  * p(k) = k | 1 and M = max_j m_j it needs

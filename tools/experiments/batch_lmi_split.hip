@@ -86,7 +86,7 @@ __global__ __launch_bounds__(T) void k_loop_clocked(BatchParams P, BatchLmiParam
         if (live) lx[i] = xci;
         __syncthreads();
         const long long t0 = wall_clock64();
-        batch_lmi_oracle(L, live, i, n, F, Bm, lx, cl, fa, wit, osc, g);
+        batch_lmi_oracle(L, live, i, n, F, Bm, nullptr, lx, cl, fa, wit, osc, g);
         const long long t1 = wall_clock64();
         const bool lane = lane_ok && osc_s[BL_STOPPED] == 0.0;
         const int kind = (lane && osc_s[LO_STATION] == shrunk_station) ? CUT_CENTRAL : CUT_BIAS;
