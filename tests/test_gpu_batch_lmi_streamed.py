@@ -125,8 +125,8 @@ CALL_SHAPES = [(129, (1,)), (129, (64, 3)), (130, (2, 63)), (192, (5, 17, 64)), 
 FORMS = [(False, False, True), (False, True, False), (True, False, False), (True, True, True)]
 
 
-@pytest.mark.parametrize("n,ms", CALL_SHAPES, ids=["%d-%s" % (n, "x".join(map(str, ms))) for n, ms in CALL_SHAPES])
-def test_oracle_call_by_call(gpu, n, ms):
+def oracle_call_by_call(gpu, n, ms):
+    """three calls of the wide oracle kernel at (n; ms) in each of FORMS, with no update in between, against RoundRobinLmi"""
     B, J = 3, len(ms)
     who = [(s, 0.0) for s in range(B)]
     mat_f, mat_b, c, _, _ = cases.stack(n, ms, who)
@@ -165,6 +165,11 @@ def test_oracle_call_by_call(gpu, n, ms):
                 assert same_bits(beta[b], bt) and same_bits(gamma_out[b], gm), (call, b, beta[b], bt, gamma_out[b], gm)
             np.testing.assert_array_equal(prob.idx, np.array([om.idx for om in omegas], dtype=np.int32))
             gamma = gamma_out
+
+
+@pytest.mark.parametrize("n,ms", CALL_SHAPES, ids=["%d-%s" % (n, "x".join(map(str, ms))) for n, ms in CALL_SHAPES])
+def test_oracle_call_by_call(gpu, n, ms):
+    oracle_call_by_call(gpu, n, ms)
 
 
 # ---- 2. the pinned runs -----------------------------------------------------------------------------------------------------
