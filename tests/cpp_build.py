@@ -67,6 +67,16 @@ def build_runner(src: str, backend: str) -> str:
     return exe
 
 
+def build_host_tool(src: str) -> str:
+    """A plain C++ program of tests/cpp that links nothing of the project (g++, -ffp-contract=off): tests/cpp/_build/<stem>."""
+    os.makedirs(OUT, exist_ok=True)
+    exe = os.path.join(OUT, os.path.splitext(src)[0])
+    deps = [os.path.join(CPP, src)] + [os.path.join(CPP, f) for f in os.listdir(CPP) if f.endswith(".hpp")]
+    if _newer(exe, deps):
+        subprocess.check_call(["g++", "-std=c++17", "-O2", "-ffp-contract=off", "-Wall", "-o", exe, os.path.join(CPP, src), "-lm"])
+    return exe
+
+
 def run_json_lines(exe, *args, timeout=600, env=None):
     import json
     full_env = None if env is None else {**os.environ, **env}

@@ -7,21 +7,31 @@ A sequence is the queue's form: (kinds int32[k], grads [k][n], beta0[k], beta1[k
     nothing under- or overflows; from |e| ~ 300 on the parallel cut's t0 * t1 ~ tsq^2 does);
   * a zero gradient (the reference's own degenerate cut, benches/ellipsoid.rs): omega = tsq = 0 -- a bias cut with
     beta = 0 or a q-cut "succeeds" and fills xc, Q and kappa with NaN, a central cut leaves kappa finite, beta > 0 is NoSoln;
-  * |g| = 1e-154 from Q0 = I: omega ~ 1e-308, a subnormal, through which the reference stays finite.
+  * |g| = 1e-154 from Q0 = I: omega ~ 1e-308, a subnormal, through which the reference stays finite;
+  * diagonally rescaled: from the start (D Q0 D, D xc0), the cuts (D^-1 g, beta) with D = diag(2^e_i), |e_i| <= 20, are the
+    same run ELEMENT BY ELEMENT -- statuses, tsq and kappa to the bit, xc' = D xc and Q' = D Q D to the bit: every term of
+    every sum the update forms (Q g, g.Qg, v_j.g) is scaled by ONE power of two per sum, every element of Q and xc by its own.
+    The per-element form of `rescaled`: it breaks on a hidden absolute constant, and on any sum that mixes elements of
+    different rows or columns.
 """
 import numpy as np
 
-from util import TOL, mixed_cut, oracle_update, stable_tau
+from util import TOL, dense_spd, mixed_cut, oracle_update, stable_tau
 
 SCALE_EXPONENTS = (-200, 200)
 SUBNORMAL_G = 1e-154
 NOSOLN_BETA = 0.1
+DIAG_EXPONENT = 20
 
 
-def mixed_seq(orc, n, k, seed, stable=False):
-    """util.mixed_cut's sequence (all six EllCalc entry points, a NoSoln cut every 8th) from kappa0 = 1, Q0 = I, xc0 = 0,
-    unit gradients, betas scaled by the tau the oracle itself sees before each cut."""
-    o = (orc.OracleEllStable if stable else orc.OracleEll).new_with_scalar(1.0, np.zeros(n))
+def mixed_seq(orc, n, k, seed, stable=False, start=None):
+    """util.mixed_cut's sequence (all six EllCalc entry points, a NoSoln cut every 8th) from kappa0 = 1, Q0 = I, xc0 = 0
+    (start = (Q0, xc0): from that matrix and centre, Ell only), unit gradients, betas scaled by the tau the oracle itself
+    sees before each cut."""
+    if start is not None:
+        o = orc.OracleEll.new_with_matrix(1.0, start[0], start[1])
+    else:
+        o = (orc.OracleEllStable if stable else orc.OracleEll).new_with_scalar(1.0, np.zeros(n))
     rng = np.random.default_rng(seed)
     kinds = np.zeros(k, dtype=np.int32)
     grads = np.empty((k, n))
@@ -49,6 +59,28 @@ def scaled(cuts, e):
     s = 2.0 ** e
     kinds, grads, b0, b1 = cuts
     return kinds.copy(), grads * s, b0 * s, b1 * s
+
+
+def diag_exponents(n, seed):
+    """e_i of D = diag(2^e_i), |e_i| <= DIAG_EXPONENT, from a seeded generator"""
+    return np.random.default_rng(seed).integers(-DIAG_EXPONENT, DIAG_EXPONENT + 1, n)
+
+
+def dense_start(n, seed, e=None):
+    """(Q0, xc0): util.dense_spd (dense, symmetric to the bit, g'Qg = O(1) for unit g) and a non-zero centre;
+    e: (D Q0 D, D xc0), exact -- every element times its own power of two."""
+    q0 = dense_spd(n, seed)
+    xc0 = np.random.default_rng(seed + 1).standard_normal(n)
+    if e is None:
+        return q0, xc0
+    d = np.ldexp(1.0, e)
+    return np.ascontiguousarray(d[:, None] * q0 * d[None, :]), d * xc0
+
+
+def diag_scaled(cuts, e):
+    """(D^-1 g, beta): the cuts that do to (D Q D, D xc) what `cuts` do to (Q, xc)"""
+    kinds, grads, b0, b1 = cuts
+    return kinds.copy(), grads * np.ldexp(1.0, -np.asarray(e))[None, :], b0.copy(), b1.copy()
 
 
 def with_zero(cuts, positions, outcome):

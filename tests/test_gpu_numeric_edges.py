@@ -6,6 +6,9 @@ the oracle does there):
     as the last recorded update of a depth-24 handle -- with both outcomes: Success (the state becomes NaN) and NoSoln (a
     queue halts, the state is the one before it);
   * a subnormal omega (|g| = 1e-154): finite where the oracle is finite;
+  * a DIAGONALLY rescaled run -- start (D Q0 D, D xc0), cuts (D^-1 g, beta), D = diag(2^e_i), |e_i| <= 20 -- is the same run
+    element by element: statuses, tsq and kappa to the bit, xc' = D xc and Q' = D Q D to the bit, on every single-handle Ell
+    schedule (a sum that mixes elements of different rows or columns, or a stale element read, breaks it);
   * the host staging path (ELLHIP_OPT_STAGE_DIRECT = 0: k_stage pulls each gradient from pinned memory) against the direct
     write, with the caller's gradient buffer overwritten as soon as each call returns.
 Each schedule is pinned by options (and the depth) on its handle, and profile_read() shows that its kernel class ran."""
@@ -14,8 +17,8 @@ from collections import namedtuple
 import numpy as np
 import pytest
 
-from numeric_edges import (SCALE_EXPONENTS, assert_state_with_nans, beta, mixed_seq, oracle_run,
-                           queue_seq, scaled, state, subnormal_seq, with_zero)
+from numeric_edges import (SCALE_EXPONENTS, assert_state_with_nans, beta, dense_start, diag_exponents, diag_scaled, mixed_seq,
+                           oracle_run, queue_seq, scaled, state, subnormal_seq, with_zero)
 from util import TOL, set_default
 
 pytestmark = pytest.mark.gpu
@@ -46,14 +49,18 @@ SCHEDULES = {
 B = 4   # members of an EllBatch
 
 
-def make(gpu, sid, n):
-    """A handle pinned to schedule `sid`, profiling on."""
+def make(gpu, sid, n, start=None):
+    """A handle pinned to schedule `sid`, profiling on.  start = (Q0, xc0): an Ell from that matrix and centre (kappa0 = 1)."""
     sp = SCHEDULES[sid]
     for k, v in sp.defaults.items():
         set_default(k, v)
     if sp.variant == "batch":
         return gpu.EllBatch.new_with_scalar(1.0, np.zeros((B, n)))
-    e = (gpu.EllStable if sp.variant == "stable" else gpu.Ell).new_with_scalar(1.0, np.zeros(n))
+    if start is not None:
+        assert sp.variant == "ell"
+        e = gpu.Ell.new_with_matrix(1.0, start[0], start[1])
+    else:
+        e = (gpu.EllStable if sp.variant == "stable" else gpu.Ell).new_with_scalar(1.0, np.zeros(n))
     if sp.depth is not None:
         e.defer_depth = sp.depth
         assert e.defer_depth == sp.depth
@@ -112,9 +119,9 @@ def drive(gpu, e, sid, cuts, buf=None):
     return st, ts
 
 
-def run(gpu, sid, n, cuts, buf=None):
+def run(gpu, sid, n, cuts, buf=None, start=None):
     """(statuses, tsq, (Q, xc, kappa), kernel launch counts) of one run on a fresh handle."""
-    e = make(gpu, sid, n)
+    e = make(gpu, sid, n, start)
     st, ts = drive(gpu, e, sid, cuts, buf)
     if SCHEDULES[sid].variant == "stable" and st[st != 3][-1] == 0:
         # (the layout holds after a successful cut until an observer rebuilds the reference's buffer; a failed cut rewrites
@@ -153,20 +160,22 @@ def _direct_k(sid):
     return 56 if sid.startswith(("low", "rec")) else 40
 
 
-def sequence(orc, sid, n, seed):
+def sequence(orc, sid, n, seed, start=None):
     sp = SCHEDULES[sid]
     if sp.drive in ("queue", "fused"):
         return queue_seq(n, 24 if sid in ("res", "st0q", "st3q") else 56, seed)
-    return mixed_seq(orc, n, _direct_k(sid), seed, stable=sp.variant == "stable")
+    return mixed_seq(orc, n, _direct_k(sid), seed, stable=sp.variant == "stable", start=start)
 
 
-def oracle_for(orc, sid, n):
+def oracle_for(orc, sid, n, start=None):
+    if start is not None:
+        return orc.OracleEll.new_with_matrix(1.0, start[0], start[1])
     return (orc.OracleEllStable if SCHEDULES[sid].variant == "stable" else orc.OracleEll).new_with_scalar(1.0, np.zeros(n))
 
 
-def check_against_oracle(orc, sid, n, cuts, st, ts, s, tol=TOL):
+def check_against_oracle(orc, sid, n, cuts, st, ts, s, tol=TOL, start=None):
     halt = SCHEDULES[sid].drive in ("queue", "fused")
-    o = oracle_for(orc, sid, n)
+    o = oracle_for(orc, sid, n, start)
     ost, ots = oracle_run(o, cuts, halt=halt)
     assert np.array_equal(st, ost), (sid, list(st), list(ost))
     last = int(np.argmax(ost != 0)) if halt and np.any(ost != 0) else len(ost) - 1
@@ -222,6 +231,36 @@ def test_rescaled_run_is_the_same_run(gpu, orc, sid, n):
         assert np.array_equal(ts2, ts * 4.0 ** e), (sid, e, np.max(np.abs(ts2 / (ts * 4.0 ** e) - 1.0)))
         for name, a, b in zip(("Q", "xc", "kappa"), s2, s):
             assert np.array_equal(a, b), (sid, e, name, np.max(np.abs(np.asarray(a) - np.asarray(b))))
+
+
+# the single-handle Ell schedules of RESCALE_CASES (EllStable and the batch engines: their packed layouts need an argument of
+# their own)
+DIAG_CASES = [(s, n) for s, n in RESCALE_CASES if SCHEDULES[s].variant == "ell" and (s, n) not in (("qmfma", 5120), ("res", 4096))]
+
+
+@pytest.mark.parametrize("sid,n", DIAG_CASES, ids=[f"{s}-{n}" for s, n in DIAG_CASES])
+def test_diagonally_rescaled_run_is_the_same_run(gpu, orc, sid, n):
+    """Q -> D Q D, xc -> D xc, g -> D^-1 g with D = diag(2^e_i), |e_i| <= 20, betas unchanged: every product and every sum of
+    the update scales by one power of two per element, so statuses, tsq and kappa keep their bits, xc' = D xc and Q' = D Q D bit
+    for bit (tests/test_numeric_edges_cpu.py pins it on the oracle).  Both runs start through new_with_matrix from
+    util.dense_spd and a non-zero centre; the unscaled one is checked against the oracle."""
+    seed = 9 * n + len(sid)
+    start = dense_start(n, seed)
+    cuts = sequence(orc, sid, n, seed=seed + 2, start=start)
+    st, ts, s, prof = run(gpu, sid, n, cuts, start=start)
+    check_profile(sid, prof, len(cuts[0]))
+    check_against_oracle(orc, sid, n, cuts, st, ts, s, start=start)
+    e = diag_exponents(n, seed + 3)
+    d = np.ldexp(1.0, e)
+    st2, ts2, (q2, xc2, kappa2), prof2 = run(gpu, sid, n, diag_scaled(cuts, e), start=dense_start(n, seed, e))
+    check_profile(sid, prof2, len(cuts[0]))
+    assert np.array_equal(st2, st), (sid, list(st2), list(st))
+    assert np.array_equal(ts2, ts), (sid, "tsq", np.max(np.abs(ts2 / ts - 1.0)))
+    assert kappa2 == s[2], (sid, "kappa", kappa2, s[2])
+    assert np.array_equal(xc2, d * s[1]), (sid, "xc", int(np.sum(xc2 != d * s[1])))
+    want = d[:, None] * s[0] * d[None, :]
+    bad = np.argwhere(q2 != want)
+    assert bad.size == 0, (sid, "Q", len(bad), bad[:4].tolist(), float(np.max(np.abs(q2 / want - 1.0))))
 
 
 @pytest.mark.parametrize("n", [16, 128])

@@ -5,8 +5,8 @@ uses, Ell and EllStable."""
 import numpy as np
 import pytest
 
-from numeric_edges import (NOSOLN_BETA, SCALE_EXPONENTS, mixed_seq, oracle_run, queue_seq, scaled, state, subnormal_seq,
-                           with_zero)
+from numeric_edges import (DIAG_EXPONENT, NOSOLN_BETA, SCALE_EXPONENTS, dense_start, diag_exponents, diag_scaled, mixed_seq,
+                           oracle_run, queue_seq, scaled, state, subnormal_seq, with_zero)
 
 # (variant, sequence, n, k, seed): the mixed sequences of the direct schedules and the queue sequences of the queued ones
 SEQUENCES = [("ell", "mixed", 64, 40, 11), ("ell", "mixed", 1000, 40, 12), ("ell", "queue", 1024, 56, 13),
@@ -46,6 +46,28 @@ def test_rescaling_breaks_down_beyond_the_exponents_used(orc):
     st2, _ = oracle_run(o2, scaled(cuts, -300))
     q, q2 = state(o)[0], state(o2)[0]
     assert not (np.array_equal(st, st2) and np.array_equal(q, q2))
+
+
+@pytest.mark.parametrize("n,kind", [(64, "mixed"), (257, "mixed"), (64, "queue"), (257, "queue")])
+def test_diagonally_rescaled_sequences_are_the_same_run_element_by_element(orc, n, kind):
+    """From (D Q0 D, D xc0) the cuts (D^-1 g, beta) give the statuses, tsq and kappa of the unscaled run to the bit, and
+    xc' = D xc, Q' = D Q D to the bit (D = diag(2^e_i), |e_i| <= 20; the cuts are built for the unscaled start)."""
+    start = dense_start(n, 41 + n)
+    cuts = mixed_seq(orc, n, 40, 17 + n, start=start) if kind == "mixed" else queue_seq(n, 40, 17 + n)
+    o = orc.OracleEll.new_with_matrix(1.0, *start)
+    st, ts = oracle_run(o, cuts)
+    q, xc, kappa = state(o)
+    assert np.all(np.isfinite(q)) and (kind == "queue") == np.all(st == 0) and np.any(xc != start[1])
+    e = diag_exponents(n, 43 + n)
+    assert e.min() <= -DIAG_EXPONENT + 3 and e.max() >= DIAG_EXPONENT - 3
+    d = np.ldexp(1.0, e)
+    o2 = orc.OracleEll.new_with_matrix(1.0, *dense_start(n, 41 + n, e))
+    st2, ts2 = oracle_run(o2, diag_scaled(cuts, e))
+    q2, xc2, kappa2 = state(o2)
+    assert np.array_equal(st2, st) and np.array_equal(ts2, ts) and kappa2 == kappa
+    assert np.array_equal(xc2, d * xc) and np.array_equal(q2, d[:, None] * q * d[None, :])
+    # what the norm-wise check makes of it: an element of the scaled Q may sit 2^-80 below the largest one
+    assert np.abs(q2).min() < 1e-12 * np.abs(q2).max()
 
 
 # kind, b0, b1 of the zero-gradient cut -> (status, kappa finite)
