@@ -14,12 +14,8 @@ from . import capi
 from .ell import _f64, _p
 
 
-def _loop_entry(spaces, name: str) -> str:
-    """the `_streamed` entry point for an EllBatchStreamed, `_streamed_stable` for an EllStableBatchStreamed
-    (include/ellhip_batch_lmi_streamed.h), else what capi.batch_loop_entry chooses"""
-    if not getattr(spaces, "is_streamed", False):
-        return capi.batch_loop_entry(spaces, name)
-    return name + ("_streamed_stable" if spaces.variant == capi.SPACE_ELL_STABLE else "_streamed")
+# the entry point `name` of the engine and the variant of a batch handle (tests import it from here)
+_loop_entry = capi.batch_loop_entry
 
 
 class BatchLmiProblem:
@@ -107,23 +103,11 @@ class BatchLmiProblem:
         EllStableBatchStreamed).  Returns (x_best [B][n] with NaN rows where there
         is none, has_best [B], niter [B], gamma [B], status [B])."""
         gamma = np.array(np.broadcast_to(np.asarray(gamma, dtype=np.float64), (self.B,)))
-        x_best = np.full((self.B, self.n), np.nan)
-        has = np.empty(self.B, dtype=np.int32)
-        niter = np.empty(self.B, dtype=np.int64)
-        status = np.empty(self.B, dtype=np.int32)
-        entry = _loop_entry(spaces, "ellhip_batch_lmi_optim")
-        capi.check(getattr(self._lib, entry)(spaces._h, self._h, _p(gamma), int(max_iters), float(tol), _p(x_best), _p(has),
-                                             _p(niter), _p(status)), entry)
+        x_best, has, niter, status = capi.run_batch_loop(self._lib, _loop_entry(spaces, "ellhip_batch_lmi_optim"), spaces, self,
+                                                         gamma, max_iters, tol)
         return x_best, has, niter, gamma, status
 
     def feas(self, spaces, max_iters: int, tol: float):
         """cutting_plane_feas per problem.  Returns (x [B][n] with NaN rows where infeasible, feasible [B], niter [B],
         status [B])."""
-        x = np.full((self.B, self.n), np.nan)
-        ok = np.empty(self.B, dtype=np.int32)
-        niter = np.empty(self.B, dtype=np.int64)
-        status = np.empty(self.B, dtype=np.int32)
-        entry = _loop_entry(spaces, "ellhip_batch_lmi_feas")
-        capi.check(getattr(self._lib, entry)(spaces._h, self._h, int(max_iters), float(tol), _p(x), _p(ok), _p(niter),
-                                             _p(status)), entry)
-        return x, ok, niter, status
+        return capi.run_batch_loop(self._lib, _loop_entry(spaces, "ellhip_batch_lmi_feas"), spaces, self, None, max_iters, tol)

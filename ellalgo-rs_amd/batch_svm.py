@@ -13,12 +13,8 @@ from . import capi
 from .ell import _f64, _p
 
 
-def _loop_entry(batch, name: str) -> str:
-    """the `_streamed` entry point for an EllBatchStreamed, `_streamed_stable` for an EllStableBatchStreamed
-    (include/ellhip_batch_svm_streamed.h), else what capi.batch_loop_entry chooses"""
-    if not getattr(batch, "is_streamed", False):
-        return capi.batch_loop_entry(batch, name)
-    return name + ("_streamed_stable" if batch.variant == capi.SPACE_ELL_STABLE else "_streamed")
+# the entry point `name` of the engine and the variant of a batch handle (tests import it from here)
+_loop_entry = capi.batch_loop_entry
 
 
 class BatchSvmProblem:
@@ -86,11 +82,6 @@ class BatchSvmProblem:
         EllStableBatchStreamed of dimension nfeat + 1).  Returns
         (x_best [B][n] with NaN rows where there is none, has_best [B], niter [B], gamma [B], status [B])."""
         gamma = np.array(np.broadcast_to(np.asarray(gamma, dtype=np.float64), (self.B,)))
-        x_best = np.full((self.B, self.n), np.nan)
-        has = np.empty(self.B, dtype=np.int32)
-        niter = np.empty(self.B, dtype=np.int64)
-        status = np.empty(self.B, dtype=np.int32)
-        entry = _loop_entry(batch, "ellhip_batch_svm_optim")
-        capi.check(getattr(self._lib, entry)(batch._h, self._h, _p(gamma), int(max_iters), float(tol), _p(x_best), _p(has),
-                                             _p(niter), _p(status)), entry)
+        x_best, has, niter, status = capi.run_batch_loop(self._lib, _loop_entry(batch, "ellhip_batch_svm_optim"), batch, self,
+                                                         gamma, max_iters, tol)
         return x_best, has, niter, gamma, status

@@ -7,6 +7,8 @@ from __future__ import annotations
 import ctypes as C
 import os
 
+import numpy as np
+
 from . import build as _build
 
 SUCCESS, NOSOLN, NOEFFECT, UNKNOWN = 0, 1, 2, 3
@@ -407,9 +409,26 @@ def load():
 
 
 def batch_loop_entry(batch, name: str) -> str:
-    """The entry point that runs loop `name` on `batch`: the Ell one, or its `_stable` sibling
-    (include/ellhip_batch_stable_loops.h) for an EllStable batch handle."""
-    return name + "_stable" if batch.variant == SPACE_ELL_STABLE else name
+    """The entry point that runs loop `name` on `batch`: the Ell one, its `_stable` sibling
+    (include/ellhip_batch_stable_loops.h) for an EllStableBatch, `_streamed` for an EllBatchStreamed and `_streamed_stable`
+    for an EllStableBatchStreamed (include/ellhip_batch_{lmi,lowpass,svm}_streamed.h,
+    ellhip_batch_lowpass_streamed_stable.h).  A handle without an `is_streamed` attribute is not streamed."""
+    streamed = "_streamed" if getattr(batch, "is_streamed", False) else ""
+    return name + streamed + ("_stable" if batch.variant == SPACE_ELL_STABLE else "")
+
+
+def run_batch_loop(lib, entry: str, batch, problem, gamma, max_iters: int, tol: float):
+    """One call of loop entry point `entry` (optim: gamma is the [B] array it updates in place; feas: gamma is None and is
+    not passed).  Returns (x [B][n] with NaN rows where the loop found no point, has [B] int32, niter [B] int64,
+    status [B] int32); a refusal raises EllHipError with the entry point's name."""
+    x = np.full((problem.B, problem.n), np.nan)
+    has = np.empty(problem.B, dtype=np.int32)
+    niter = np.empty(problem.B, dtype=np.int64)
+    status = np.empty(problem.B, dtype=np.int32)
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p)
+    args = ([] if gamma is None else [ptr(gamma)]) + [int(max_iters), float(tol), ptr(x), ptr(has), ptr(niter), ptr(status)]
+    check(getattr(lib, entry)(batch._h, problem._h, *args), entry)
+    return x, has, niter, status
 
 
 def check(rc: int, what: str = "") -> int:

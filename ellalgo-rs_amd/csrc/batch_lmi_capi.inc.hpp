@@ -37,15 +37,17 @@ BatchLmiOracle::Args batch_lmi_args(const ellhip_batch_lmi* o) {
     return A;
 }
 
-// stable: the spaces are EllStable (include/ellhip_batch_stable_loops.h)
+// The loops of all four headers (ellhip_batch_lmi.h, ellhip_batch_stable_loops.h, ellhip_batch_lmi_streamed.h) on `engine`.
+// Which of optim and feas a handle serves is refused in the words of the engine's Ell entry points.
 int batch_lmi_run(ellhip_batch* s, ellhip_batch_lmi* o, int feas, double* gamma_inout, int64_t max_iters, double tol,
-                  double* x_out, int32_t* has_out, int64_t* niter_out, int32_t* status_out, bool stable = false) {
+                  double* x_out, int32_t* has_out, int64_t* niter_out, int32_t* status_out, BatchLoopEngine engine) {
     if (!s || !o || !has_out || !niter_out || !status_out || (!feas && !gamma_inout))
         return fail(ELLHIP_E_INVALID, "NULL argument");
-    if (!feas && !o->L.has_c) return fail(ELLHIP_E_INVALID, "batched LMI loop: optim needs a handle made with c");
-    if (feas && o->L.has_c) return fail(ELLHIP_E_INVALID, "batched LMI loop: feas needs a handle made without c");
-    return batch_loop_run<BatchLmiOracle>(s, o->loop, batch_lmi_args(o), {"batched LMI loop", "(n, m)", ""}, stable, feas,
-                                          gamma_inout, max_iters, tol, x_out, has_out, niter_out, status_out);
+    const std::string what = batch_loop_what("LMI", {engine.streamed, false});
+    if (!feas && !o->L.has_c) return fail(ELLHIP_E_INVALID, (what + ": optim needs a handle made with c").c_str());
+    if (feas && o->L.has_c) return fail(ELLHIP_E_INVALID, (what + ": feas needs a handle made without c").c_str());
+    return batch_loop_run<BatchLmiOracle>(s, o->loop, batch_lmi_args(o), {"LMI", "(n, m)", ""}, engine, feas, gamma_inout,
+                                          max_iters, tol, x_out, has_out, niter_out, status_out);
 }
 
 // The constructor of both headers.  nmax: 128 for ellhip_batch_lmi_create, 1024 for ellhip_batch_lmi_create_streamed
@@ -225,12 +227,13 @@ int ellhip_batch_lmi_set_idx(ellhip_batch_lmi* o, const int32_t* idx) {
 
 int ellhip_batch_lmi_optim(ellhip_batch* spaces, ellhip_batch_lmi* o, double* gamma_inout, int64_t max_iters, double tol,
                            double* x_best_out, int32_t* has_best_out, int64_t* niter_out, int32_t* status_out) {
-    return batch_lmi_run(spaces, o, 0, gamma_inout, max_iters, tol, x_best_out, has_best_out, niter_out, status_out);
+    return batch_lmi_run(spaces, o, 0, gamma_inout, max_iters, tol, x_best_out, has_best_out, niter_out, status_out,
+                         BATCH_ENGINE_LDS);
 }
 
 int ellhip_batch_lmi_feas(ellhip_batch* spaces, ellhip_batch_lmi* o, int64_t max_iters, double tol, double* x_out,
                           int32_t* feasible_out, int64_t* niter_out, int32_t* status_out) {
-    return batch_lmi_run(spaces, o, 1, nullptr, max_iters, tol, x_out, feasible_out, niter_out, status_out);
+    return batch_lmi_run(spaces, o, 1, nullptr, max_iters, tol, x_out, feasible_out, niter_out, status_out, BATCH_ENGINE_LDS);
 }
 
 int ellhip_batch_lmi_set_chunk(ellhip_batch_lmi* o, int64_t iters) {

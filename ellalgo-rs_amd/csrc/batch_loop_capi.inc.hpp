@@ -1,10 +1,15 @@
 // batch_loop_capi.inc.hpp -- the host side the batched device-resident cutting-plane loops share: the loop state an oracle
-// handle owns, the launch shapes and the one driver that runs k_batch_loop (batch_loop_kernels.hpp) over a batch handle.
-// Included at the end of ellhip_capi.hip, after batch_capi.inc.hpp (it drives the batch engine's handle directly) and
-// before batch_lmi_capi.inc.hpp, batch_lowpass_capi.inc.hpp and batch_svm_capi.inc.hpp.
+// handle owns, the launch shapes and the one driver that runs the loop kernel of a batch engine -- k_batch_loop
+// (batch_loop_kernels.hpp) on the LDS engine, k_batch_streamed_loop (batch_streamed_loop_kernels.hpp) and
+// k_batch_streamed_loop_stable (batch_streamed_stable_loop_kernels.hpp) on the streamed one -- over a batch handle.
+// Included at the end of ellhip_capi.hip, after batch_capi.inc.hpp, batch_streamed_capi.inc.hpp and
+// batch_streamed_stable_capi.inc.hpp (it drives the batch engines' handle directly) and before every batch_*_capi.inc.hpp
+// of an oracle.
 //
 // Reference: src/cutting_plane.rs:205-227, 286-313 (loops).
 #include "batch_loop_kernels.hpp"
+#include "batch_streamed_loop_kernels.hpp"
+#include "batch_streamed_stable_loop_kernels.hpp"
 
 namespace {
 
@@ -79,18 +84,20 @@ int batch_loop_set_chunk(BatchLoopBuffers* st, int64_t iters, const char* what) 
 // 160 KiB per workgroup, less the 1 KiB kept for the kernel's static LDS (the barrier votes)
 constexpr size_t BATCH_LOOP_LDS_MAX = 159 * 1024;
 
-// more than the default 64 KiB of dynamic LDS needs an opt-in per kernel and per device; as in batch_shape it is only ever
-// raised, with the high-water marks kept per (oracle, device, block size)
-template <class Oracle>
-int batch_loop_allow_lds(const void* kernel, int device, int slot, size_t bytes) {
+// More than the default 64 KiB of dynamic LDS needs an opt-in per kernel and per device; a launch within 64 KiB needs none
+// and never comes past the first line.  As in batch_shape it is only ever raised; the high-water marks are the kernel's own
+// (one instantiation of this function, and so one table, per kernel instantiation).
+template <auto Kernel>
+int batch_loop_allow_lds(int device, size_t bytes) {
     constexpr int MAXDEV = 64;
-    static std::atomic<int> granted[MAXDEV][6];  // T = 64, 128, 256 on Ell, then on EllStable
+    static std::atomic<int> granted[MAXDEV];
+    if (bytes <= 64 * 1024) return 0;
     const bool known = device >= 0 && device < MAXDEV;
-    if (known && (int)bytes <= granted[device][slot].load()) return 0;
-    HIPCHK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    if (known && (int)bytes <= granted[device].load()) return 0;
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
     if (known) {
-        int seen = granted[device][slot].load();
-        while (seen < (int)bytes && !granted[device][slot].compare_exchange_weak(seen, (int)bytes)) {}
+        int seen = granted[device].load();
+        while (seen < (int)bytes && !granted[device].compare_exchange_weak(seen, (int)bytes)) {}
     }
     return 0;
 }
@@ -108,12 +115,11 @@ BatchRowShape batch_row_shape(int n, size_t doubles) {
     return r;
 }
 
-// How the loop kernel is launched on a batch handle.  An Ell handle is launched as the batch engine shaped it.  An EllStable
-// handle is shaped for k_batch_update_stable's one lane per ellipsoid (one wave, up to 64 ellipsoids); the loop kernel
-// gives an instance n threads, so it takes batch_row_shape with batch_stable_apply_lds_doubles in it.  slot: the entry of
-// batch_loop_allow_lds's table.
+// How k_batch_loop is launched on a batch handle of the LDS engine.  An Ell handle is launched as the batch engine shaped
+// it.  An EllStable handle is shaped for k_batch_update_stable's one lane per ellipsoid (one wave, up to 64 ellipsoids); the
+// loop kernel gives an instance n threads, so it takes batch_row_shape with batch_stable_apply_lds_doubles in it.
 struct BatchLoopShape {
-    int T = 64, epw = 1, slot = 0;
+    int T = 64, epw = 1;
     size_t space_doubles = 0;  // LDS doubles of one instance's space
 };
 
@@ -129,22 +135,47 @@ BatchLoopShape batch_loop_shape(const ellhip_batch* s, bool stable) {
         sh.T = r.T;
         sh.epw = r.epw;
     }
-    sh.slot = (sh.T == 64 ? 0 : (sh.T == 128 ? 1 : 2)) + (stable ? 3 : 0);
     return sh;
 }
 
-// the handle's variant against the entry point's: the plain entry points take Ell handles, the _stable ones EllStable
-int batch_loop_check(const ellhip_batch* s, bool stable, const char* what) {
-    const int want = stable ? ELLHIP_SPACE_ELL_STABLE : ELLHIP_SPACE_ELL;
-    if (s->streamed)  // the loop kernel keeps the matrix in LDS (include/ellhip_batch_streamed.h)
-        return fail(ELLHIP_E_INVALID, (std::string(what) + ": streamed batch handles are not supported").c_str());
-    if (s->variant == want) return 0;
-    const std::string msg = std::string(what) + (stable ? ": the _stable entry points take EllStable batch handles only"
-                                                        : ": EllStable batch handles are not supported");
-    return fail(ELLHIP_E_INVALID, msg.c_str());
+// The engine an entry point runs on: the LDS engine (include/ellhip_batch.h) or the streamed one
+// (include/ellhip_batch_streamed.h), with Ell or with EllStable spaces.  The plain entry points are {false, false}; the
+// suffixes _stable, _streamed and _streamed_stable name the other three.
+struct BatchLoopEngine {
+    bool streamed, stable;
+};
+constexpr BatchLoopEngine BATCH_ENGINE_LDS{false, false}, BATCH_ENGINE_LDS_STABLE{false, true},
+    BATCH_ENGINE_STREAMED{true, false}, BATCH_ENGINE_STREAMED_STABLE{true, true};
+
+// What a refusal calls the oracle, the shape and the dimension; what it calls the loop comes from the engine.
+struct BatchLoopWords {
+    const char* oracle;  // "LMI"
+    const char* shape;   // "(n, m)": what decides the LDS an instance needs
+    const char* n_is;    // "" or how the oracle's n comes about
+};
+
+// "batched LMI loop" on both LDS engines (the _stable entry points share the plain ones' words), "batched LMI streamed loop",
+// "batched LMI streamed EllStable loop"
+std::string batch_loop_what(const char* oracle, BatchLoopEngine e) {
+    return std::string("batched ") + oracle + (!e.streamed ? " loop" : e.stable ? " streamed EllStable loop" : " streamed loop");
 }
 
-BatchParams batch_loop_params(const ellhip_batch* s, const BatchLoopShape& sh) {
+// the handle's kind against the entry point's engine: first the engine (a streamed handle keeps its matrices in HBM, the LDS
+// engine's kernel keeps them in LDS), then the variant
+int batch_loop_check(const ellhip_batch* s, BatchLoopEngine e, const std::string& what) {
+    const std::string entry =
+        std::string("the ") + (e.streamed ? "_streamed" : "") + (e.stable ? "_stable" : "") + " entry points take ";
+    if (e.streamed && !s->streamed) return fail(ELLHIP_E_INVALID, (what + ": " + entry + "streamed batch handles only").c_str());
+    if (!e.streamed && s->streamed) return fail(ELLHIP_E_INVALID, (what + ": streamed batch handles are not supported").c_str());
+    if (s->variant == (e.stable ? ELLHIP_SPACE_ELL_STABLE : ELLHIP_SPACE_ELL)) return 0;
+    return fail(ELLHIP_E_INVALID, (what + ": " + (e.stable ? entry + "EllStable batch handles only"
+                                                          : "EllStable batch handles are not supported")).c_str());
+}
+
+template <int T, bool STABLE, class Oracle>
+int batch_loop_launch(const ellhip_batch* s, const BatchLoopShape& sh, size_t lds, const BatchLoopRun& R,
+                      const BatchLoopState& S, const typename Oracle::Args& A, const EllCalcDev& calc) {
+    if (const int rc = batch_loop_allow_lds<&k_batch_loop<T, STABLE, Oracle>>(s->device, lds)) return rc;
     BatchParams P;
     P.B = s->B;
     P.n = s->n;
@@ -152,27 +183,33 @@ BatchParams batch_loop_params(const ellhip_batch* s, const BatchLoopShape& sh) {
     P.epw = sh.epw;
     P.K = 0;
     P.no_defer_trick = s->no_defer_trick;
-    return P;
-}
-
-template <int T, bool STABLE, class Oracle>
-int batch_loop_launch(const ellhip_batch* s, const BatchLoopShape& sh, size_t lds, const BatchParams& P, const BatchLoopRun& R,
-                      const BatchLoopState& S, const typename Oracle::Args& A, const EllCalcDev& calc) {
-    if (const int rc = batch_loop_allow_lds<Oracle>(reinterpret_cast<const void*>(&k_batch_loop<T, STABLE, Oracle>), s->device,
-                                                    sh.slot, lds))
-        return rc;
     const unsigned grid = (unsigned)((s->B + sh.epw - 1) / sh.epw);
     hipLaunchKernelGGL((k_batch_loop<T, STABLE, Oracle>), dim3(grid), dim3(T), lds, s->stream, P, R, s->d_Q, s->d_xc,
                        s->d_kappa, s->d_tsq, S, A, calc);
     return 0;
 }
 
-// What a refusal calls the loop, the shape and the dimension (the messages are the entry points' own).
-struct BatchLoopWords {
-    const char* what;   // "batched LMI loop"
-    const char* shape;  // "(n, m)": what decides the LDS an instance needs
-    const char* n_is;   // "" or how the oracle's n comes about
-};
+// one workgroup per instance, the block the streamed handle was shaped with
+template <bool STABLE, class Oracle>
+int batch_streamed_loop_launch(const ellhip_batch* s, size_t lds, const BatchLoopRun& R, const BatchLoopState& S,
+                               const typename Oracle::Args& A, const EllCalcDev& calc) {
+    BatchStreamedParams P;
+    P.B = s->B;
+    P.n = s->n;
+    P.np = batch_streamed_np(s->n);
+    P.K = 0;
+    P.no_defer_trick = STABLE ? 0 : s->no_defer_trick;  // Ell only: the EllStable handle refuses the setter
+    if constexpr (STABLE) {
+        if (const int rc = batch_loop_allow_lds<&k_batch_streamed_loop_stable<Oracle>>(s->device, lds)) return rc;
+        hipLaunchKernelGGL(k_batch_streamed_loop_stable<Oracle>, dim3((unsigned)s->B), dim3(s->T), lds, s->stream, P, R, s->d_Q,
+                           s->d_xc, s->d_kappa, s->d_tsq, S, A, calc);
+    } else {
+        if (const int rc = batch_loop_allow_lds<&k_batch_streamed_loop<Oracle>>(s->device, lds)) return rc;
+        hipLaunchKernelGGL(k_batch_streamed_loop<Oracle>, dim3((unsigned)s->B), dim3(s->T), lds, s->stream, P, R, s->d_Q, s->d_xc,
+                           s->d_kappa, s->d_tsq, s->d_sym, S, A, calc);
+    }
+    return 0;
+}
 
 // The part of a run that does not depend on the kernel: cutting_plane_optim (feas = 0, gamma in and out) or
 // cutting_plane_feas for every instance, up to max_iters rounds in launches of st.chunk until every instance has stopped,
@@ -221,32 +258,37 @@ int batch_loop_drive(ellhip_batch* s, BatchLoopBuffers& st, int feas, double* ga
     return 0;
 }
 
-// The loops on the LDS engine: k_batch_loop over a batch handle of Ell spaces, or of EllStable spaces (stable:
-// include/ellhip_batch_stable_loops.h).  The caller has checked its pointers.
+// The loops of one oracle on one engine: the loop kernel of `engine` over a batch handle of that engine's kind.  The caller
+// has checked its pointers.
 template <class Oracle>
-int batch_loop_run(ellhip_batch* s, BatchLoopBuffers& st, const typename Oracle::Args& A,
-                   const BatchLoopWords& w, bool stable, int feas, double* gamma_inout, int64_t max_iters, double tol,
-                   double* x_out, int32_t* has_out, int64_t* niter_out, int32_t* status_out) {
-    const std::string what(w.what);
-    if (const int rc = batch_loop_check(s, stable, w.what)) return rc;
+int batch_loop_run(ellhip_batch* s, BatchLoopBuffers& st, const typename Oracle::Args& A, const BatchLoopWords& w,
+                   BatchLoopEngine engine, int feas, double* gamma_inout, int64_t max_iters, double tol, double* x_out,
+                   int32_t* has_out, int64_t* niter_out, int32_t* status_out) {
+    const std::string what = batch_loop_what(w.oracle, engine);
+    if (const int rc = batch_loop_check(s, engine, what)) return rc;
     if (s->B != st.B || s->n != st.n)
         return fail(ELLHIP_E_INVALID, (what + ": spaces and oracle differ in B or n" + w.n_is).c_str());
     if (s->device != st.device) return fail(ELLHIP_E_INVALID, (what + ": spaces and oracle live on different devices").c_str());
-    const BatchLoopShape sh = batch_loop_shape(s, stable);
-    const size_t lds = (size_t)sh.epw * (sh.space_doubles + Oracle::lds_doubles(A, s->n)) * sizeof(double);
+    const BatchLoopShape sh = engine.streamed ? BatchLoopShape{} : batch_loop_shape(s, engine.stable);  // the LDS engine's
+    const size_t doubles = !engine.streamed ? (size_t)sh.epw * (sh.space_doubles + Oracle::lds_doubles(A, s->n))
+                           : engine.stable  ? batch_streamed_stable_loop_lds_doubles<Oracle>(A, s->n)
+                                            : batch_streamed_loop_lds_doubles<Oracle>(A, s->n);
+    const size_t lds = doubles * sizeof(double);
     if (lds > BATCH_LOOP_LDS_MAX)
         return fail(ELLHIP_E_INVALID, (what + ": this " + w.shape + " needs more LDS than a workgroup has").c_str());
-    const BatchParams P = batch_loop_params(s, sh);
     const EllCalcDev calc = EllCalcDev::make(s->n, s->use_parallel_cut);
     const BatchLoopState S = batch_loop_view(st);
     return batch_loop_drive(s, st, feas, gamma_inout, max_iters, tol, x_out, has_out, niter_out, status_out,
                             [&](const BatchLoopRun& R) {
-        if (stable)
-            return sh.T == 128 ? batch_loop_launch<128, true, Oracle>(s, sh, lds, P, R, S, A, calc)
-                               : batch_loop_launch<256, true, Oracle>(s, sh, lds, P, R, S, A, calc);
-        return sh.T == 64    ? batch_loop_launch<64, false, Oracle>(s, sh, lds, P, R, S, A, calc)
-               : sh.T == 128 ? batch_loop_launch<128, false, Oracle>(s, sh, lds, P, R, S, A, calc)
-                             : batch_loop_launch<256, false, Oracle>(s, sh, lds, P, R, S, A, calc);
+        if (engine.streamed)
+            return engine.stable ? batch_streamed_loop_launch<true, Oracle>(s, lds, R, S, A, calc)
+                                 : batch_streamed_loop_launch<false, Oracle>(s, lds, R, S, A, calc);
+        if (engine.stable)
+            return sh.T == 128 ? batch_loop_launch<128, true, Oracle>(s, sh, lds, R, S, A, calc)
+                               : batch_loop_launch<256, true, Oracle>(s, sh, lds, R, S, A, calc);
+        return sh.T == 64    ? batch_loop_launch<64, false, Oracle>(s, sh, lds, R, S, A, calc)
+               : sh.T == 128 ? batch_loop_launch<128, false, Oracle>(s, sh, lds, R, S, A, calc)
+                             : batch_loop_launch<256, false, Oracle>(s, sh, lds, R, S, A, calc);
     });
 }
 

@@ -60,14 +60,15 @@ int batch_lowpass_fresh(ellhip_batch_lowpass* o) {
     return 0;
 }
 
-// stable: the spaces are EllStable (include/ellhip_batch_stable_loops.h)
+// the loops of all four headers (ellhip_batch_lowpass.h, ellhip_batch_stable_loops.h, ellhip_batch_lowpass_streamed.h,
+// ellhip_batch_lowpass_streamed_stable.h) on `engine`
 int batch_lowpass_run(ellhip_batch* s, ellhip_batch_lowpass* o, int feas, double* gamma_inout, int64_t max_iters,
                       double tol, double* x_out, int32_t* has_out, int64_t* niter_out, int32_t* status_out,
-                      bool stable = false) {
+                      BatchLoopEngine engine) {
     if (!s || !o || !has_out || !niter_out || !status_out || (!feas && !gamma_inout))
         return fail(ELLHIP_E_INVALID, "NULL argument");
-    return batch_loop_run<BatchLpOracle>(s, o->loop, batch_lowpass_args(o), {"batched lowpass loop", "n", ""}, stable, feas,
-                                         gamma_inout, max_iters, tol, x_out, has_out, niter_out, status_out);
+    return batch_loop_run<BatchLpOracle>(s, o->loop, batch_lowpass_args(o), {"lowpass", "n", ""}, engine, feas, gamma_inout,
+                                         max_iters, tol, x_out, has_out, niter_out, status_out);
 }
 
 // one oracle call per problem; ans[B] = BLP_*
@@ -120,7 +121,7 @@ int batch_lowpass_assess(ellhip_batch_lowpass* o, int optim, const double* x, do
     return 0;
 }
 
-// nmax: 128 for the LDS engine's constructor, 1024 for the streamed one (batch_streamed_loop_capi.inc.hpp)
+// nmax: 128 for the LDS engine's constructor, 1024 for the streamed one (batch_lowpass_streamed_capi.inc.hpp)
 int batch_lowpass_create(ellhip_batch_lowpass** out, int64_t B, int64_t n, const double* wpass, const double* wstop,
                          const double* lp_sq, const double* up_sq, const double* sp_sq, const double* spectrum, int device,
                          int nmax) {
@@ -288,12 +289,14 @@ int ellhip_batch_lowpass_get_spectrum(ellhip_batch_lowpass* o, double* out) {
 int ellhip_batch_lowpass_optim(ellhip_batch* spaces, ellhip_batch_lowpass* o, double* gamma_inout, int64_t max_iters,
                                double tol, double* x_best_out, int32_t* has_best_out, int64_t* niter_out,
                                int32_t* status_out) {
-    return batch_lowpass_run(spaces, o, 0, gamma_inout, max_iters, tol, x_best_out, has_best_out, niter_out, status_out);
+    return batch_lowpass_run(spaces, o, 0, gamma_inout, max_iters, tol, x_best_out, has_best_out, niter_out, status_out,
+                             BATCH_ENGINE_LDS);
 }
 
 int ellhip_batch_lowpass_feas(ellhip_batch* spaces, ellhip_batch_lowpass* o, int64_t max_iters, double tol, double* x_out,
                               int32_t* feasible_out, int64_t* niter_out, int32_t* status_out) {
-    return batch_lowpass_run(spaces, o, 1, nullptr, max_iters, tol, x_out, feasible_out, niter_out, status_out);
+    return batch_lowpass_run(spaces, o, 1, nullptr, max_iters, tol, x_out, feasible_out, niter_out, status_out,
+                             BATCH_ENGINE_LDS);
 }
 
 int ellhip_batch_lowpass_set_chunk(ellhip_batch_lowpass* o, int64_t iters) {

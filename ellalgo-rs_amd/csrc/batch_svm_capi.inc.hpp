@@ -194,18 +194,19 @@ int ellhip_batch_svm_last(ellhip_batch_svm* o, int64_t* min_idx, double* min_val
     return 0;
 }
 
-// stable: the spaces are EllStable (include/ellhip_batch_stable_loops.h)
+// the loop of all three headers (ellhip_batch_svm.h, ellhip_batch_stable_loops.h, ellhip_batch_svm_streamed.h) on `engine`
 static int batch_svm_run(ellhip_batch* s, ellhip_batch_svm* o, double* gamma_inout, int64_t max_iters, double tol,
-                         double* x_best_out, int32_t* has_best_out, int64_t* niter_out, int32_t* status_out, bool stable) {
+                         double* x_best_out, int32_t* has_best_out, int64_t* niter_out, int32_t* status_out,
+                         BatchLoopEngine engine) {
     if (!s || !o || !gamma_inout || !has_best_out || !niter_out || !status_out)
         return fail(ELLHIP_E_INVALID, "NULL argument");
-    return batch_loop_run<BatchSvmOracle>(s, o->loop, batch_svm_args(o), {"batched svm loop", "n", " (n = nfeat + 1)"}, stable,
-                                          0, gamma_inout, max_iters, tol, x_best_out, has_best_out, niter_out, status_out);
+    return batch_loop_run<BatchSvmOracle>(s, o->loop, batch_svm_args(o), {"svm", "n", " (n = nfeat + 1)"}, engine, 0,
+                                          gamma_inout, max_iters, tol, x_best_out, has_best_out, niter_out, status_out);
 }
 
 int ellhip_batch_svm_optim(ellhip_batch* s, ellhip_batch_svm* o, double* gamma_inout, int64_t max_iters, double tol,
                            double* x_best_out, int32_t* has_best_out, int64_t* niter_out, int32_t* status_out) {
-    return batch_svm_run(s, o, gamma_inout, max_iters, tol, x_best_out, has_best_out, niter_out, status_out, false);
+    return batch_svm_run(s, o, gamma_inout, max_iters, tol, x_best_out, has_best_out, niter_out, status_out, BATCH_ENGINE_LDS);
 }
 
 int ellhip_batch_svm_set_chunk(ellhip_batch_svm* o, int64_t iters) {

@@ -1,9 +1,9 @@
 // batch_svm_streamed_capi.inc.hpp -- C ABI of the batched device-resident SVM cutting-plane loop on streamed batch handles,
 // Ell and EllStable (include/ellhip_batch_svm_streamed.h).  Included at the end of ellhip_capi.hip,
-// after batch_svm_capi.inc.hpp (the oracle handle and batch_svm_create), batch_streamed_loop_capi.inc.hpp
-// (batch_streamed_loop_run) and batch_streamed_stable_loop_capi.inc.hpp (batch_streamed_stable_loop_run).
+// after batch_svm_capi.inc.hpp (the oracle handle, batch_svm_create and batch_svm_run, which reaches both kernels through
+// batch_loop_run of batch_loop_capi.inc.hpp).
 //
-// Nothing here but two instantiations: k_batch_streamed_loop<BatchSvmOracle> and k_batch_streamed_loop_stable<BatchSvmOracle>
+// Nothing here but two engines of that driver: k_batch_streamed_loop<BatchSvmOracle> and k_batch_streamed_loop_stable<BatchSvmOracle>
 // take the policy k_batch_loop takes (batch_svm_kernels.hpp), whose scan is mapped onto "the n threads of an instance" with
 // a stride of n and so is tied neither to an instance-per-workgroup count nor to n <= 128.  The block is n rounded up to 64
 // threads; threads i >= n are inactive in the oracle (live = false) and take part in each of its barriers.  Bounds: every
@@ -13,23 +13,6 @@
 //
 // Reference: src/oracles/svm_oracle.rs:4-58 (oracle), src/cutting_plane.rs:286-313 (loop).
 #include "../../include/ellhip_batch_svm_streamed.h"
-
-namespace {
-
-int batch_svm_run_streamed(ellhip_batch* s, ellhip_batch_svm* o, double* gamma_inout, int64_t max_iters, double tol,
-                           double* x_best_out, int32_t* has_best_out, int64_t* niter_out, int32_t* status_out, bool stable) {
-    if (!s || !o || !gamma_inout || !has_best_out || !niter_out || !status_out)
-        return fail(ELLHIP_E_INVALID, "NULL argument");
-    if (stable)
-        return batch_streamed_stable_loop_run<BatchSvmOracle>(
-            s, o->loop, batch_svm_args(o), {"batched svm streamed EllStable loop", "n", " (n = nfeat + 1)"}, 0, gamma_inout,
-            max_iters, tol, x_best_out, has_best_out, niter_out, status_out);
-    return batch_streamed_loop_run<BatchSvmOracle>(s, o->loop, batch_svm_args(o),
-                                                   {"batched svm streamed loop", "n", " (n = nfeat + 1)"}, 0, gamma_inout,
-                                                   max_iters, tol, x_best_out, has_best_out, niter_out, status_out);
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -41,15 +24,15 @@ int ellhip_batch_svm_create_streamed(ellhip_batch_svm** out, int64_t B, int64_t 
 int ellhip_batch_svm_optim_streamed(ellhip_batch* spaces, ellhip_batch_svm* o, double* gamma_inout, int64_t max_iters,
                                     double tol, double* x_best_out, int32_t* has_best_out, int64_t* niter_out,
                                     int32_t* status_out) {
-    return batch_svm_run_streamed(spaces, o, gamma_inout, max_iters, tol, x_best_out, has_best_out, niter_out, status_out,
-                                  false);
+    return batch_svm_run(spaces, o, gamma_inout, max_iters, tol, x_best_out, has_best_out, niter_out, status_out,
+                         BATCH_ENGINE_STREAMED);
 }
 
 int ellhip_batch_svm_optim_streamed_stable(ellhip_batch* spaces, ellhip_batch_svm* o, double* gamma_inout, int64_t max_iters,
                                            double tol, double* x_best_out, int32_t* has_best_out, int64_t* niter_out,
                                            int32_t* status_out) {
-    return batch_svm_run_streamed(spaces, o, gamma_inout, max_iters, tol, x_best_out, has_best_out, niter_out, status_out,
-                                  true);
+    return batch_svm_run(spaces, o, gamma_inout, max_iters, tol, x_best_out, has_best_out, niter_out, status_out,
+                         BATCH_ENGINE_STREAMED_STABLE);
 }
 
 }  // extern "C"

@@ -2973,7 +2973,7 @@ int ellhip_profile_read(ellhip_space* s, double* ms_out, int64_t* count_out) {
 #include "batch_svm_capi.inc.hpp"
 #include "lmi_loop_capi.inc.hpp"
 #include "batch_stable_loops_capi.inc.hpp"
-#include "batch_streamed_loop_capi.inc.hpp"
-#include "batch_streamed_stable_loop_capi.inc.hpp"
+#include "batch_lowpass_streamed_capi.inc.hpp"
+#include "batch_lowpass_streamed_stable_capi.inc.hpp"
 #include "batch_svm_streamed_capi.inc.hpp"
 #include "batch_lmi_streamed_capi.inc.hpp"

@@ -60,40 +60,28 @@ class BatchLmiHip {
     // or an EllStableBatchStreamedHip through include/ellhip_batch_lmi_streamed.h)
     template <int VARIANT, bool STREAMED>
     BatchLmiResult optim(BatchHip<VARIANT, STREAMED>& spaces, Arr& gamma, const Options& options) {
-        constexpr bool stable = VARIANT == ELLHIP_SPACE_ELL_STABLE;
         if (gamma.size() != B_) throw Error(ELLHIP_E_INVALID, "gamma must have B entries");
         Arr x(B_ * n_);
         std::vector<int32_t> has(B_), status(B_);
         std::vector<int64_t> niter(B_);
-        const auto entry = STREAMED && stable ? ellhip_batch_lmi_optim_streamed_stable
-                           : STREAMED         ? ellhip_batch_lmi_optim_streamed
-                           : stable           ? ellhip_batch_lmi_optim_stable
-                                              : ellhip_batch_lmi_optim;
-        check(entry(spaces.handle(), h_, gamma.data(), (int64_t)options.max_iters, options.tolerance, x.data(), has.data(),
+        const auto entry = loop_entry(spaces, "ellhip_batch_lmi_optim", ellhip_batch_lmi_optim, ellhip_batch_lmi_optim_stable,
+                                      ellhip_batch_lmi_optim_streamed, ellhip_batch_lmi_optim_streamed_stable);
+        check(entry.fn(spaces.handle(), h_, gamma.data(), (int64_t)options.max_iters, options.tolerance, x.data(), has.data(),
                     niter.data(), status.data()),
-              STREAMED && stable ? "ellhip_batch_lmi_optim_streamed_stable"
-              : STREAMED         ? "ellhip_batch_lmi_optim_streamed"
-              : stable           ? "ellhip_batch_lmi_optim_stable"
-                                 : "ellhip_batch_lmi_optim");
+              entry.name.c_str());
         return result(x, has, niter, status);
     }
     // cutting_plane_feas (:205-227) for every problem
     template <int VARIANT, bool STREAMED>
     BatchLmiResult feas(BatchHip<VARIANT, STREAMED>& spaces, const Options& options) {
-        constexpr bool stable = VARIANT == ELLHIP_SPACE_ELL_STABLE;
         Arr x(B_ * n_);
         std::vector<int32_t> has(B_), status(B_);
         std::vector<int64_t> niter(B_);
-        const auto entry = STREAMED && stable ? ellhip_batch_lmi_feas_streamed_stable
-                           : STREAMED         ? ellhip_batch_lmi_feas_streamed
-                           : stable           ? ellhip_batch_lmi_feas_stable
-                                              : ellhip_batch_lmi_feas;
-        check(entry(spaces.handle(), h_, (int64_t)options.max_iters, options.tolerance, x.data(), has.data(), niter.data(),
+        const auto entry = loop_entry(spaces, "ellhip_batch_lmi_feas", ellhip_batch_lmi_feas, ellhip_batch_lmi_feas_stable,
+                                      ellhip_batch_lmi_feas_streamed, ellhip_batch_lmi_feas_streamed_stable);
+        check(entry.fn(spaces.handle(), h_, (int64_t)options.max_iters, options.tolerance, x.data(), has.data(), niter.data(),
                     status.data()),
-              STREAMED && stable ? "ellhip_batch_lmi_feas_streamed_stable"
-              : STREAMED         ? "ellhip_batch_lmi_feas_streamed"
-              : stable           ? "ellhip_batch_lmi_feas_stable"
-                                 : "ellhip_batch_lmi_feas");
+              entry.name.c_str());
         return result(x, has, niter, status);
     }
     std::vector<int32_t> idx() const {

@@ -91,40 +91,30 @@ class BatchLowpassHip {
     // include/ellhip_batch_lowpass_streamed_stable.h)
     template <int VARIANT, bool STREAMED>
     BatchLowpassResult optim(BatchHip<VARIANT, STREAMED>& spaces, Arr& gamma, const Options& options) {
-        constexpr bool stable = VARIANT == ELLHIP_SPACE_ELL_STABLE;
         if (gamma.size() != B_) throw Error(ELLHIP_E_INVALID, "gamma must have B entries");
         Arr x(B_ * n_);
         std::vector<int32_t> has(B_), status(B_);
         std::vector<int64_t> niter(B_);
-        const auto entry = STREAMED && stable ? ellhip_batch_lowpass_optim_streamed_stable
-                           : STREAMED         ? ellhip_batch_lowpass_optim_streamed
-                           : stable           ? ellhip_batch_lowpass_optim_stable
-                                              : ellhip_batch_lowpass_optim;
-        check(entry(spaces.handle(), h_, gamma.data(), (int64_t)options.max_iters, options.tolerance, x.data(), has.data(),
+        const auto entry = loop_entry(spaces, "ellhip_batch_lowpass_optim", ellhip_batch_lowpass_optim,
+                                      ellhip_batch_lowpass_optim_stable, ellhip_batch_lowpass_optim_streamed,
+                                      ellhip_batch_lowpass_optim_streamed_stable);
+        check(entry.fn(spaces.handle(), h_, gamma.data(), (int64_t)options.max_iters, options.tolerance, x.data(), has.data(),
                     niter.data(), status.data()),
-              STREAMED && stable ? "ellhip_batch_lowpass_optim_streamed_stable"
-              : STREAMED         ? "ellhip_batch_lowpass_optim_streamed"
-              : stable           ? "ellhip_batch_lowpass_optim_stable"
-                                 : "ellhip_batch_lowpass_optim");
+              entry.name.c_str());
         return result(x, has, niter, status);
     }
     // cutting_plane_feas (:205-227) for every problem
     template <int VARIANT, bool STREAMED>
     BatchLowpassResult feas(BatchHip<VARIANT, STREAMED>& spaces, const Options& options) {
-        constexpr bool stable = VARIANT == ELLHIP_SPACE_ELL_STABLE;
         Arr x(B_ * n_);
         std::vector<int32_t> has(B_), status(B_);
         std::vector<int64_t> niter(B_);
-        const auto entry = STREAMED && stable ? ellhip_batch_lowpass_feas_streamed_stable
-                           : STREAMED         ? ellhip_batch_lowpass_feas_streamed
-                           : stable           ? ellhip_batch_lowpass_feas_stable
-                                              : ellhip_batch_lowpass_feas;
-        check(entry(spaces.handle(), h_, (int64_t)options.max_iters, options.tolerance, x.data(), has.data(), niter.data(),
+        const auto entry = loop_entry(spaces, "ellhip_batch_lowpass_feas", ellhip_batch_lowpass_feas,
+                                      ellhip_batch_lowpass_feas_stable, ellhip_batch_lowpass_feas_streamed,
+                                      ellhip_batch_lowpass_feas_streamed_stable);
+        check(entry.fn(spaces.handle(), h_, (int64_t)options.max_iters, options.tolerance, x.data(), has.data(), niter.data(),
                     status.data()),
-              STREAMED && stable ? "ellhip_batch_lowpass_feas_streamed_stable"
-              : STREAMED         ? "ellhip_batch_lowpass_feas_streamed"
-              : stable           ? "ellhip_batch_lowpass_feas_stable"
-                                 : "ellhip_batch_lowpass_feas");
+              entry.name.c_str());
         return result(x, has, niter, status);
     }
     std::vector<Fields> fields() const {

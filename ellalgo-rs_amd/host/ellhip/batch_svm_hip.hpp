@@ -84,21 +84,15 @@ class BatchSvmHip {
     // or an EllStableBatchStreamedHip through include/ellhip_batch_svm_streamed.h)
     template <int VARIANT, bool STREAMED>
     BatchSvmResult optim(BatchHip<VARIANT, STREAMED>& spaces, Arr& gamma, const Options& options) {
-        constexpr bool stable = VARIANT == ELLHIP_SPACE_ELL_STABLE;
         if (gamma.size() != B_) throw Error(ELLHIP_E_INVALID, "gamma must have B entries");
         Arr x(B_ * n_);
         std::vector<int32_t> has(B_), status(B_);
         std::vector<int64_t> niter(B_);
-        const auto entry = STREAMED && stable ? ellhip_batch_svm_optim_streamed_stable
-                           : STREAMED         ? ellhip_batch_svm_optim_streamed
-                           : stable           ? ellhip_batch_svm_optim_stable
-                                              : ellhip_batch_svm_optim;
-        check(entry(spaces.handle(), h_, gamma.data(), (int64_t)options.max_iters, options.tolerance, x.data(), has.data(),
+        const auto entry = loop_entry(spaces, "ellhip_batch_svm_optim", ellhip_batch_svm_optim, ellhip_batch_svm_optim_stable,
+                                      ellhip_batch_svm_optim_streamed, ellhip_batch_svm_optim_streamed_stable);
+        check(entry.fn(spaces.handle(), h_, gamma.data(), (int64_t)options.max_iters, options.tolerance, x.data(), has.data(),
                     niter.data(), status.data()),
-              STREAMED && stable ? "ellhip_batch_svm_optim_streamed_stable"
-              : STREAMED         ? "ellhip_batch_svm_optim_streamed"
-              : stable           ? "ellhip_batch_svm_optim_stable"
-                                 : "ellhip_batch_svm_optim");
+              entry.name.c_str());
         BatchSvmResult r;
         for (std::size_t b = 0; b < B_; ++b) {
             if (has[b]) r.x_best.emplace_back(Arr(x.begin() + b * n_, x.begin() + (b + 1) * n_));

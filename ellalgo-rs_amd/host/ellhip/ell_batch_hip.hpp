@@ -9,6 +9,7 @@
 #pragma once
 
 #include <cstdint>
+#include <string>
 #include <vector>
 
 #include "../../../include/ellhip_batch.h"
@@ -165,5 +166,21 @@ using EllBatchHip = BatchHip<ELLHIP_SPACE_ELL>;
 using EllStableBatchHip = BatchHip<ELLHIP_SPACE_ELL_STABLE>;
 using EllBatchStreamedHip = BatchHip<ELLHIP_SPACE_ELL, true>;
 using EllStableBatchStreamedHip = BatchHip<ELLHIP_SPACE_ELL_STABLE, true>;
+
+// The entry point of a batched loop for the engine and the variant of a batch handle: `plain` on an EllBatchHip, else its
+// sibling `base`_stable (include/ellhip_batch_stable_loops.h), `base`_streamed or `base`_streamed_stable; with the name that
+// check() reports.
+template <class Fn>
+struct LoopEntry {
+    Fn* fn;
+    std::string name;
+};
+template <int VARIANT, bool STREAMED, class Fn>
+LoopEntry<Fn> loop_entry(const BatchHip<VARIANT, STREAMED>&, const char* base, Fn* plain, Fn* stable, Fn* streamed,
+                         Fn* streamed_stable) {
+    constexpr bool STABLE = VARIANT == ELLHIP_SPACE_ELL_STABLE;
+    return {STREAMED ? (STABLE ? streamed_stable : streamed) : (STABLE ? stable : plain),
+            std::string(base) + (STREAMED ? "_streamed" : "") + (STABLE ? "_stable" : "")};
+}
 
 }  // namespace ellhip

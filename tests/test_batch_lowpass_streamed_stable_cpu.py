@@ -57,11 +57,11 @@ def test_symbol_exported(name):
 def test_sources_are_in_the_build_recipe():
     import ellalgo_rs_amd as pkg
     assert "batch_streamed_stable_loop_kernels.hpp" in pkg.build.HEADERS
-    assert "batch_streamed_stable_loop_capi.inc.hpp" in pkg.build.HEADERS
+    assert "batch_lowpass_streamed_stable_capi.inc.hpp" in pkg.build.HEADERS
     assert "ellhip_batch_lowpass_streamed_stable.h" in pkg.build.PUBLIC_HEADERS
     main = open(os.path.join(pkg.build.CSRC, "ellhip_capi.hip")).read()
-    inc = open(os.path.join(pkg.build.CSRC, "batch_streamed_stable_loop_capi.inc.hpp")).read()
-    assert main.index('#include "batch_streamed_loop_capi.inc.hpp"') < main.index('#include "batch_streamed_stable_loop_capi.inc.hpp"')
+    inc = open(os.path.join(pkg.build.CSRC, "batch_loop_capi.inc.hpp")).read()
+    assert main.index('#include "batch_lowpass_capi.inc.hpp"') < main.index('#include "batch_lowpass_streamed_stable_capi.inc.hpp"')
     assert '#include "batch_streamed_stable_loop_kernels.hpp"' in inc
     kernels = open(os.path.join(pkg.build.CSRC, "batch_streamed_stable_loop_kernels.hpp")).read()
     assert "bs_stable_cut(" in kernels and '#include "batch_streamed_stable_kernels.hpp"' in kernels

@@ -125,4 +125,5 @@ def test_host_mirror_dispatches_on_the_batch_variant(tmp_path):
     for name in ("batch_lmi_hip.hpp", "batch_lowpass_hip.hpp", "batch_svm_hip.hpp"):
         text = open(os.path.join(host, name)).read()
         stem = name[len("batch_"):-len("_hip.hpp")]
-        assert f"ellhip_batch_{stem}_optim_stable" in text and "ELLHIP_SPACE_ELL_STABLE" in text
+        assert f"ellhip_batch_{stem}_optim_stable" in text and "loop_entry(spaces, " in text
+    assert "ELLHIP_SPACE_ELL_STABLE" in open(os.path.join(host, "ell_batch_hip.hpp")).read().split("loop_entry(const BatchHip")[1]

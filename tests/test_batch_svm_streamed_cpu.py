@@ -106,10 +106,13 @@ def test_sources_are_in_the_build_recipe():
     assert "ellhip_batch_svm_streamed.h" in pkg.build.PUBLIC_HEADERS
     main = open(os.path.join(pkg.build.CSRC, "ellhip_capi.hip")).read()
     new = main.index('#include "batch_svm_streamed_capi.inc.hpp"')
-    for dep in ("batch_svm_capi.inc.hpp", "batch_streamed_loop_capi.inc.hpp", "batch_streamed_stable_loop_capi.inc.hpp"):
+    for dep in ("batch_svm_capi.inc.hpp", "batch_loop_capi.inc.hpp"):
         assert main.index(f'#include "{dep}"') < new
     inc = open(os.path.join(pkg.build.CSRC, "batch_svm_streamed_capi.inc.hpp")).read()
-    assert "batch_streamed_loop_run<BatchSvmOracle>" in inc and "batch_streamed_stable_loop_run<BatchSvmOracle>" in inc
+    assert "batch_svm_run(" in inc and "BATCH_ENGINE_STREAMED)" in inc and "BATCH_ENGINE_STREAMED_STABLE)" in inc
+    assert "batch_loop_run<BatchSvmOracle>" in open(os.path.join(pkg.build.CSRC, "batch_svm_capi.inc.hpp")).read()
+    driver = open(os.path.join(pkg.build.CSRC, "batch_loop_capi.inc.hpp")).read()
+    assert "k_batch_streamed_loop<Oracle>" in driver and "k_batch_streamed_loop_stable<Oracle>" in driver
 
 
 def test_python_mirror_picks_the_entry_point_by_handle():
