@@ -1152,11 +1152,68 @@ __device__ __forceinline__ void pk_stage_sgr(const double* __restrict__ gP, long
         sgr[row + 4][col] = v.y;
     }
 }
+// The block loops of the 32-wide product pass and of the fused pass, piece by piece (template argument PL of symm_tile2 /
+// apply_symm_tile; 0 = the loops as round 6 left them, kept for tests/cpp/pass_pipeline_check.hip).  No piece changes an MFMA's
+// operands or the order in which an accumulator takes them: Q, rowpart and colpart are the same bits for every PL.
+//   PL_ROTATE  the loop is rotated: the wave's first block is loaded ahead of the loop, and block b + 4 is loaded right after
+//              block b has gone to the wave's LDS patch -- into x[] (and, fused pass, bv[]), which are dead from there on -- so
+//              that the round trip runs behind the 16 NVT row-product MFMAs instead of in front of the trip's first MFMA;
+//   PL_SGR2    the strip's A operands lie in LDS as pairs, sgr2[((t 8 + j2) 64 + lane) 2 + e] = gT[r0 + 4 (2 j2 + e) + lr][16 t + lc]:
+//              one 16-byte read per two column-product MFMAs (the same 16 KiB inside the same array);
+//   PL_ACC     fused pass: each of the four update accumulators takes all its k-steps back to back.
+constexpr int PL_ROTATE = 1, PL_SGR2 = 2, PL_ACC = 4;
+constexpr int SYMM2_PL = PL_ROTATE | PL_SGR2;
+constexpr int APPLY_SYMM_PL = PL_ROTATE | PL_SGR2 | PL_ACC;
+// PL_ROTATE, ahead of the guarded loads of block b + 4: everything issued so far (this block's gc, its Q stores, the column sums of
+// block b - 4 -- all at least one product phase old) has returned.  The compiler counts vmcnt along the path WITHOUT the guarded
+// loads, so a wait for gc placed after them would wait for them as well; after this one the row products need none, and the
+// wait for x[] at the top of the next trip counts the column-sum stores and gc loads issued behind the prefetch.
+__device__ __forceinline__ void pl_drain_vmem() {
+    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0), expcnt and lgkmcnt left alone
+}
+template <bool B>
+struct PlConst {
+    static constexpr bool value = B;
+};
+struct PlValue {
+    bool value;
+};
+// the wave's index, in a scalar register: block columns, row addresses and the loop's branch stay off the vector unit
+__device__ __forceinline__ int pl_wave() { return __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); }
+
+// the paired layout of the strip's A operands (PL_SGR2), from gP -- whose 16-byte entries are these pairs -- and from gT[c][NVW]
+template <int NVT>
+__device__ __forceinline__ void pk_stage_sgr2(const double* __restrict__ gP, long long r0, double* __restrict__ sgr2) {
+    const double2_t* p = reinterpret_cast<const double2_t*>(gP) + (r0 >> 4) * (NVT * 128);
+    for (int k = threadIdx.x; k < 4 * NVT * 128; k += 256) {
+        const int blk = k / (NVT * 128), t = (k >> 7) % NVT, kb2 = (k >> 6) & 1, ln = k & 63;
+        reinterpret_cast<double2_t*>(sgr2)[(t * 8 + 2 * blk + kb2) * 64 + ln] = p[k];
+    }
+}
+template <int NVT>
+__device__ __forceinline__ void stage_sgr2(const double* __restrict__ gT, long long r0, double* __restrict__ sgr2) {
+    constexpr int NVW = SMM_NV * NVT;
+    for (int k = threadIdx.x; k < SYMV_H * NVW; k += 256) {
+        const int row = k / NVW, col = k % NVW;
+        sgr2[(((col >> 4) * 8 + (row >> 3)) * 64 + 16 * (row & 3) + (col & 15)) * 2 + ((row >> 2) & 1)] = gT[(r0 + row) * NVW + col];
+    }
+}
+
 // a lane's column sums of tile t, block column cb + lc of strip I: pairs (o[0], o[1]) -> p = 8 t + lr, (o[2], o[3]) -> p + 4
 __device__ __forceinline__ void pk_store_colsums(double* __restrict__ colpart2, long long colpart_stride, long long I, long long n,
                                                  long long c, int t, int lr, int lv, const double4_t& dc) {
     const int p0 = 8 * t + lr;
     double* q = colpart2 + 2 * ((long long)p0 * colpart_stride + I * n + c);
+    if (2 * p0 < lv) *reinterpret_cast<double2_t*>(q) = double2_t{dc.x, dc.y};
+    if (2 * (p0 + 4) < lv) *reinterpret_cast<double2_t*>(q + 8 * colpart_stride) = double2_t{dc.z, dc.w};
+}
+
+// the same stores from the lane's base lbase = colpart2 + 2 (lr colpart_stride + I n + lc), computed once per tile: what is added
+// per block and tile t is wave-uniform
+__device__ __forceinline__ void pk_store_colsums_at(double* __restrict__ lbase, long long colpart_stride, long long cb, int t, int lr,
+                                                    int lv, const double4_t& dc) {
+    const int p0 = 8 * t + lr;
+    double* q = lbase + 2 * ((long long)(8 * t) * colpart_stride + cb);
     if (2 * p0 < lv) *reinterpret_cast<double2_t*>(q) = double2_t{dc.x, dc.y};
     if (2 * (p0 + 4) < lv) *reinterpret_cast<double2_t*>(q + 8 * colpart_stride) = double2_t{dc.z, dc.w};
 }
@@ -1327,17 +1384,27 @@ __global__ __launch_bounds__(256) void k_symm_mfma_q(const double* __restrict__ 
 // k_symm_mfma's: the partial sums of 32 gradients are bit-identical to those of two 16-wide passes, in 0.445 ms against 0.55-0.62
 // (n = 16384, tools/experiments/symm32_queue.hip).
 constexpr int SMM_NV2 = 2 * SMM_NV;
-template <bool NT, int SEG, bool PK = false>
+template <bool NT, int SEG, bool PK = false, int PL = SYMM2_PL>
 __device__ __forceinline__ void symm_tile2(const double* __restrict__ Q, long long ld, long long n, long long row0, long long I,
                                            long long J, const double* __restrict__ gT, int lv, double* __restrict__ rowpart,
                                            double* __restrict__ colpart, long long rowpart_stride, long long colpart_stride,
                                            double (*sh)[SYMV_H * SMM_PITCH], double (*sgr)[SMM_NV2 + 1]) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    constexpr bool ROT = (PL & PL_ROTATE) != 0, SGR2 = (PL & PL_SGR2) != 0;
+    const int lane = threadIdx.x & 63, wave = ROT ? pl_wave() : (int)(threadIdx.x >> 6);
+    if constexpr ((PL & PL_ROTATE) != 0) {  // (the tile index came through LDS: uniform, but not to the compiler)
+        I = __builtin_amdgcn_readfirstlane((int)I);
+        J = __builtin_amdgcn_readfirstlane((int)J);
+    }
     const int lr = lane >> 4, lc = lane & 15;
     const long long r0 = row0 + I * SYMV_H;
     const long long c0 = J * SEG;
     const bool full = c0 + SEG - 1 < r0;
-    if constexpr (PK) {
+    double* sgr2 = &sgr[0][0];
+    if constexpr (SGR2 && PK) {
+        pk_stage_sgr2<2>(gT, r0, sgr2);
+    } else if constexpr (SGR2) {
+        stage_sgr2<2>(gT, r0, sgr2);
+    } else if constexpr (PK) {
         pk_stage_sgr<2>(gT, r0, sgr);
     } else {
         for (int k = threadIdx.x; k < SYMV_H * SMM_NV2; k += 256) sgr[k / SMM_NV2][k % SMM_NV2] = gT[(r0 + k / SMM_NV2) * SMM_NV2 + k % SMM_NV2];
@@ -1352,11 +1419,19 @@ __device__ __forceinline__ void symm_tile2(const double* __restrict__ Q, long lo
     const int nblk = (int)((cend - c0) / 16);
     double* mysh = sh[wave];
     const double* qbase = Q + (r0 + lr) * ld + lc;
-    for (int b = wave; b < nblk; b += 4) {
-        const long long cb = c0 + 16 * (long long)b;
-        double x[16], gc[2][4];
+    double* cbase = colpart + 2 * ((long long)lr * colpart_stride + I * n + lc);  // (packed column sums, PL_ROTATE)
+    double x[16];
+    auto load_block = [&](long long cb) {
 #pragma unroll
         for (int j = 0; j < 16; ++j) x[j] = ld_stream<NT, double>(qbase + (long long)(4 * j) * ld + cb);
+    };
+    if constexpr (ROT) {
+        if (wave < nblk) load_block(c0 + 16 * (long long)wave);
+    }
+    for (int b = wave; b < nblk; b += 4) {
+        const long long cb = c0 + 16 * (long long)b;
+        double gc[2][4];
+        if constexpr (!ROT) load_block(cb);
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
             if constexpr (PK) {
@@ -1367,46 +1442,63 @@ __device__ __forceinline__ void symm_tile2(const double* __restrict__ Q, long lo
             }
         }
         const bool diag = !full && cb + 15 >= r0;
+        const int dg = (int)(cb - r0) + lc - lr;  // column - row of x[0]: element j is below the diagonal when dg < 4 j
         double4_t dc[2] = {double4_t{0.0, 0.0, 0.0, 0.0}, double4_t{0.0, 0.0, 0.0, 0.0}};
 #pragma unroll
         for (int t = 0; t < 2; ++t)
 #pragma unroll
-            for (int j = 0; j < 16; ++j) {
-                const long long r = r0 + 4 * j + lr, c = cb + lc;
-                const double below = (!diag || c < r) ? x[j] : 0.0;  // column sums: strictly below the diagonal
-                dc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(sgr[4 * j + lr][16 * t + lc], below, dc[t], 0, 0, 0);
+            for (int j = 0; j < 16; j += 2) {
+                const double below0 = (!diag || dg < 4 * j) ? x[j] : 0.0;  // column sums: strictly below the diagonal
+                const double below1 = (!diag || dg < 4 * j + 4) ? x[j + 1] : 0.0;
+                double2_t a;
+                if constexpr (SGR2) a = *reinterpret_cast<const double2_t*>(&sgr2[((t * 8 + j / 2) * 64 + lane) * 2]);
+                else a = double2_t{sgr[4 * j + lr][16 * t + lc], sgr[4 * j + 4 + lr][16 * t + lc]};
+                dc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a.x, below0, dc[t], 0, 0, 0);
+                dc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a.y, below1, dc[t], 0, 0, 0);
             }
         if (diag) {
 #pragma unroll
-            for (int j = 0; j < 16; ++j) {
-                const long long r = r0 + 4 * j + lr, c = cb + lc;
-                x[j] = (c <= r) ? x[j] : 0.0;  // row sums: the diagonal counts once, here
-            }
+            for (int j = 0; j < 16; ++j) x[j] = (dg <= 4 * j) ? x[j] : 0.0;  // row sums: the diagonal counts once, here
         }
 #pragma unroll
         for (int j = 0; j < 16; ++j) mysh[(4 * j + lr) * SMM_PITCH + lc] = x[j];
+        auto store_colsums = [&] {
 #pragma unroll
-        for (int t = 0; t < 2; ++t)
+            for (int t = 0; t < 2; ++t) {
+                if constexpr (PK) {
+                    if constexpr (ROT) pk_store_colsums_at(cbase, colpart_stride, cb, t, lr, lv, dc[t]);
+                    else pk_store_colsums(colpart, colpart_stride, I, n, cb + lc, t, lr, lv, dc[t]);
+                } else {
+                    const double o[4] = {dc[t].x, dc[t].y, dc[t].z, dc[t].w};
 #pragma unroll
-            for (int jj = 0; jj < 4; ++jj)
-#pragma unroll
-                for (int kb = 0; kb < 4; ++kb) {
-                    const double tv = mysh[(16 * jj + lc) * SMM_PITCH + 4 * kb + lr];
-                    dr[t][jj] = __builtin_amdgcn_mfma_f64_16x16x4f64(gc[t][kb], tv, dr[t][jj], 0, 0, 0);
-                }
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            if constexpr (PK) {
-                pk_store_colsums(colpart, colpart_stride, I, n, cb + lc, t, lr, lv, dc[t]);
-            } else {
-                const double o[4] = {dc[t].x, dc[t].y, dc[t].z, dc[t].w};
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const int v = 16 * t + lr + 4 * i;
-                    if (v < lv) colpart[(long long)v * colpart_stride + I * n + cb + lc] = o[i];
+                    for (int i = 0; i < 4; ++i) {
+                        const int v = 16 * t + lr + 4 * i;
+                        if (v < lv) colpart[(long long)v * colpart_stride + I * n + cb + lc] = o[i];
+                    }
                 }
             }
+        };
+        auto row_products = [&] {
+#pragma unroll
+            for (int t = 0; t < 2; ++t)
+#pragma unroll
+                for (int jj = 0; jj < 4; ++jj)
+#pragma unroll
+                    for (int kb = 0; kb < 4; ++kb) {
+                        const double tv = mysh[(16 * jj + lc) * SMM_PITCH + 4 * kb + lr];
+                        dr[t][jj] = __builtin_amdgcn_mfma_f64_16x16x4f64(gc[t][kb], tv, dr[t][jj], 0, 0, 0);
+                    }
+        };
+        if constexpr (ROT) {  // x[] is free: the next block's round trip runs behind the row products
+            __builtin_amdgcn_sched_barrier(0);
+            pl_drain_vmem();
+            store_colsums();  // ahead of the loads: whoever waits for the loads has waited for these
+            if (b + 4 < nblk) load_block(cb + 64);
+            __builtin_amdgcn_sched_barrier(0);
         }
+        row_products();
+        if constexpr (ROT) __builtin_amdgcn_sched_barrier(0);  // (the copies into the loop-carried x[] wait for the loads: not among the MFMAs)
+        else store_colsums();
     }
     __syncthreads();
     double* red = &sh[0][0];
@@ -1431,7 +1523,7 @@ __device__ __forceinline__ void symm_tile2(const double* __restrict__ Q, long lo
     }
 }
 
-template <bool NT, int SEG, bool PK = false>
+template <bool NT, int SEG, bool PK = false, int PL = SYMM2_PL>
 __global__ __launch_bounds__(256, 2) void k_symm_mfma_q2(const double* __restrict__ Q, long long ld, long long n, long long row0,
                                                          const double* __restrict__ gT, int lv, double* __restrict__ rowpart,
                                                          double* __restrict__ colpart, long long rowpart_stride,
@@ -1439,7 +1531,7 @@ __global__ __launch_bounds__(256, 2) void k_symm_mfma_q2(const double* __restric
                                                          const SymmTile* __restrict__ tiles, int ntiles,
                                                          unsigned* __restrict__ queue) {
     __shared__ double sh[4][SYMV_H * SMM_PITCH];
-    __shared__ double sgr[SYMV_H][SMM_NV2 + 1];  // the gT rows of the strip (odd pitch)
+    __shared__ alignas(16) double sgr[SYMV_H][SMM_NV2 + 1];  // the gT rows of the strip (odd pitch; PL_SGR2: in pairs)
     __shared__ int s_t;
     if (st->halted) return;
     Q -= row0 * ld;
@@ -1452,7 +1544,7 @@ __global__ __launch_bounds__(256, 2) void k_symm_mfma_q2(const double* __restric
         __syncthreads();
         const int t = s_t;
         if (t < 0) return;
-        symm_tile2<NT, SEG, PK>(Q, ld, n, row0, (long long)tiles[t].I, (long long)tiles[t].J, gT, lv, rowpart, colpart,
+        symm_tile2<NT, SEG, PK, PL>(Q, ld, n, row0, (long long)tiles[t].I, (long long)tiles[t].J, gT, lv, rowpart, colpart,
                                 rowpart_stride, colpart_stride, sh, sgr);
     }
 }
@@ -1474,7 +1566,7 @@ __global__ __launch_bounds__(256, 2) void k_symm_mfma_q2(const double* __restric
 // kernels do nothing once it has.  Here: the update always, the products only while st->halted is clear.
 // Unsharded handles only (row0 = 0, n % 64 == 0: every strip full, so k_apply_mfma's row and column limits never cut a block).
 // LDS: sh (34 KiB) + sgr (16.5 KiB) + the strip's A operands (64 NP doubles: 24 KiB at NP = 48) -- two workgroups per CU.
-template <int NP, bool NT, int SEG, bool WIDE, bool PK = false>
+template <int NP, bool NT, int SEG, bool WIDE, bool PK = false, int PL = APPLY_SYMM_PL>
 __device__ __forceinline__ void apply_symm_tile(double* __restrict__ Q, long long ld, long long n, long long I, long long J,
                                                 const double* __restrict__ pend, const double* __restrict__ cpend,
                                                 const double* __restrict__ gT, int lv, double* __restrict__ rowpart,
@@ -1484,7 +1576,11 @@ __device__ __forceinline__ void apply_symm_tile(double* __restrict__ Q, long lon
     constexpr int KS = NP / 4;
     constexpr int NVT = WIDE ? 2 : 1;      // 16-wide column tiles of the product
     constexpr int NVW = SMM_NV * NVT;      // row pitch of gT
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63, wave = (PL & PL_ROTATE) ? pl_wave() : (int)(threadIdx.x >> 6);
+    if constexpr ((PL & PL_ROTATE) != 0) {  // (the tile index came through LDS: uniform, but not to the compiler)
+        I = __builtin_amdgcn_readfirstlane((int)I);
+        J = __builtin_amdgcn_readfirstlane((int)J);
+    }
     const int lr = lane >> 4, lc = lane & 15;
     const long long r0 = I * SYMV_H;
     const long long c0 = J * SEG;
@@ -1496,8 +1592,14 @@ __device__ __forceinline__ void apply_symm_tile(double* __restrict__ Q, long lon
         const int k = 4 * s + (ln >> 4);
         sa[((q * (KS / 2) + s / 2) * 64 + ln) * 2 + (s & 1)] = -(cpend[k] * pend[(long long)k * n + r0 + 16 * q + (ln & 15)]);
     }
+    constexpr bool ROT = (PL & PL_ROTATE) != 0, SGR2 = (PL & PL_SGR2) != 0, ACC = (PL & PL_ACC) != 0;
+    double* sgr2 = &sgr[0][0];
     if (prod) {
-        if constexpr (PK) {
+        if constexpr (SGR2 && PK) {
+            pk_stage_sgr2<NVT>(gT, r0, sgr2);
+        } else if constexpr (SGR2) {
+            stage_sgr2<NVT>(gT, r0, sgr2);
+        } else if constexpr (PK) {
             pk_stage_sgr<NVT>(gT, r0, sgr);
         } else {
             for (int k = threadIdx.x; k < SYMV_H * NVW; k += 256) sgr[k / NVW][k % NVW] = gT[(r0 + k / NVW) * NVW + k % NVW];
@@ -1514,9 +1616,9 @@ __device__ __forceinline__ void apply_symm_tile(double* __restrict__ Q, long lon
     double* mysh = sh[wave];
     double* qbase = Q + (r0 + lr) * ld + lc;
     const double* pbase = pend + (long long)lr * n + lc;
-    for (int b = wave; b < nblk; b += 4) {
-        const long long cb = c0 + 16 * (long long)b;
-        double x[16], bv[KS], gc[NVT][4];
+    double* cbase = colpart + 2 * ((long long)lr * colpart_stride + I * n + lc);  // (packed column sums, PL_ROTATE)
+    double x[16], bv[KS];
+    auto load_block = [&](long long cb) {
 #pragma unroll
         for (int j = 0; j < 16; ++j) x[j] = ld_stream<NT, double>(qbase + (long long)(4 * j) * ld + cb);
         if constexpr (PK) {
@@ -1530,6 +1632,17 @@ __device__ __forceinline__ void apply_symm_tile(double* __restrict__ Q, long lon
 #pragma unroll
             for (int s = 0; s < KS; ++s) bv[s] = pbase[(long long)(4 * s) * n + cb];
         }
+    };
+    // (rotated: one copy of the loop per state of the queue -- behind a run-time `prod` the compiler holds the halted path's
+    // prefetch against the registers of the product phases and waits for this block's Q stores before it touches them)
+    auto block_loop = [&](auto pc) __attribute__((always_inline)) {
+    if constexpr (ROT) {
+        if (wave < nblk) load_block(c0 + 16 * (long long)wave);
+    }
+    for (int b = wave; b < nblk; b += 4) {
+        const long long cb = c0 + 16 * (long long)b;
+        double gc[NVT][4];
+        if constexpr (!ROT) load_block(cb);
         // (the phases are kept apart: with the row-sum accumulators live across the loop, 256 registers hold one phase's
         // operands at a time, not the scheduler's hoisted loads of all three)
         __builtin_amdgcn_sched_barrier(0);
@@ -1537,15 +1650,28 @@ __device__ __forceinline__ void apply_symm_tile(double* __restrict__ Q, long lon
         double4_t acc[4];
 #pragma unroll
         for (int q = 0; q < 4; ++q) acc[q] = double4_t{x[4 * q], x[4 * q + 1], x[4 * q + 2], x[4 * q + 3]};
-#pragma unroll
-        for (int s2 = 0; s2 < KS / 2; ++s2)
+        if constexpr (ACC) {  // every accumulator's k-steps back to back
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-                const double2_t a = *reinterpret_cast<const double2_t*>(&sa[((q * (KS / 2) + s2) * 64 + lane) * 2]);
-                acc[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(a.x, bv[2 * s2], acc[q], 0, 0, 0);
-                acc[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(a.y, bv[2 * s2 + 1], acc[q], 0, 0, 0);
-                if (q == 3) __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int s2 = 0; s2 < KS / 2; ++s2) {
+                    const double2_t a = *reinterpret_cast<const double2_t*>(&sa[((q * (KS / 2) + s2) * 64 + lane) * 2]);
+                    acc[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(a.x, bv[2 * s2], acc[q], 0, 0, 0);
+                    acc[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(a.y, bv[2 * s2 + 1], acc[q], 0, 0, 0);
+                }
+                __builtin_amdgcn_sched_barrier(0);
             }
+        } else {
+#pragma unroll
+            for (int s2 = 0; s2 < KS / 2; ++s2)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const double2_t a = *reinterpret_cast<const double2_t*>(&sa[((q * (KS / 2) + s2) * 64 + lane) * 2]);
+                    acc[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(a.x, bv[2 * s2], acc[q], 0, 0, 0);
+                    acc[q] = __builtin_amdgcn_mfma_f64_16x16x4f64(a.y, bv[2 * s2 + 1], acc[q], 0, 0, 0);
+                    if (q == 3) __builtin_amdgcn_sched_barrier(0);
+                }
+        }
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             x[4 * q] = acc[q].x;
@@ -1556,7 +1682,13 @@ __device__ __forceinline__ void apply_symm_tile(double* __restrict__ Q, long lon
         // 2. back to Q (default policy, as k_apply_mfma stores)
 #pragma unroll
         for (int j = 0; j < 16; ++j) qbase[(long long)(4 * j) * ld + cb] = x[j];
-        if (!prod) continue;  // (uniform)
+        if (!pc.value) {  // (uniform)
+            if constexpr (ROT) {
+                __builtin_amdgcn_sched_barrier(0);
+                if (b + 4 < nblk) load_block(cb + 64);
+            }
+            continue;
+        }
         __builtin_amdgcn_sched_barrier(0);
         // 3. the products, as symm_tile2 forms them
 #pragma unroll
@@ -1569,48 +1701,72 @@ __device__ __forceinline__ void apply_symm_tile(double* __restrict__ Q, long lon
             }
         }
         const bool diag = !full && cb + 15 >= r0;
+        const int dg = (int)(cb - r0) + lc - lr;  // column - row of x[0]: element j is below the diagonal when dg < 4 j
         double4_t dc[NVT];
 #pragma unroll
         for (int t = 0; t < NVT; ++t) {
             dc[t] = double4_t{0.0, 0.0, 0.0, 0.0};
 #pragma unroll
-            for (int j = 0; j < 16; ++j) {
-                const long long r = r0 + 4 * j + lr, c = cb + lc;
-                const double below = (!diag || c < r) ? x[j] : 0.0;  // column sums: strictly below the diagonal
-                dc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(sgr[4 * j + lr][16 * t + lc], below, dc[t], 0, 0, 0);
+            for (int j = 0; j < 16; j += 2) {
+                const double below0 = (!diag || dg < 4 * j) ? x[j] : 0.0;  // column sums: strictly below the diagonal
+                const double below1 = (!diag || dg < 4 * j + 4) ? x[j + 1] : 0.0;
+                double2_t a;
+                if constexpr (SGR2) a = *reinterpret_cast<const double2_t*>(&sgr2[((t * 8 + j / 2) * 64 + lane) * 2]);
+                else a = double2_t{sgr[4 * j + lr][16 * t + lc], sgr[4 * j + 4 + lr][16 * t + lc]};
+                dc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a.x, below0, dc[t], 0, 0, 0);
+                dc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(a.y, below1, dc[t], 0, 0, 0);
             }
         }
         if (diag) {
 #pragma unroll
-            for (int j = 0; j < 16; ++j) {
-                const long long r = r0 + 4 * j + lr, c = cb + lc;
-                x[j] = (c <= r) ? x[j] : 0.0;  // row sums: the diagonal counts once, here
-            }
+            for (int j = 0; j < 16; ++j) x[j] = (dg <= 4 * j) ? x[j] : 0.0;  // row sums: the diagonal counts once, here
         }
 #pragma unroll
         for (int j = 0; j < 16; ++j) mysh[(4 * j + lr) * SMM_PITCH + lc] = x[j];
+        auto store_colsums = [&] {
 #pragma unroll
-        for (int t = 0; t < NVT; ++t)
+            for (int t = 0; t < NVT; ++t) {
+                if constexpr (PK) {
+                    if constexpr (ROT) pk_store_colsums_at(cbase, colpart_stride, cb, t, lr, lv, dc[t]);
+                    else pk_store_colsums(colpart, colpart_stride, I, n, cb + lc, t, lr, lv, dc[t]);
+                } else {
+                    const double o[4] = {dc[t].x, dc[t].y, dc[t].z, dc[t].w};
 #pragma unroll
-            for (int jj = 0; jj < 4; ++jj)
-#pragma unroll
-                for (int kb = 0; kb < 4; ++kb) {
-                    const double tv = mysh[(16 * jj + lc) * SMM_PITCH + 4 * kb + lr];
-                    dr[t][jj] = __builtin_amdgcn_mfma_f64_16x16x4f64(gc[t][kb], tv, dr[t][jj], 0, 0, 0);
-                }
-#pragma unroll
-        for (int t = 0; t < NVT; ++t) {
-            if constexpr (PK) {
-                pk_store_colsums(colpart, colpart_stride, I, n, cb + lc, t, lr, lv, dc[t]);
-            } else {
-                const double o[4] = {dc[t].x, dc[t].y, dc[t].z, dc[t].w};
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const int v = 16 * t + lr + 4 * i;
-                    if (v < lv) colpart[(long long)v * colpart_stride + I * n + cb + lc] = o[i];
+                    for (int i = 0; i < 4; ++i) {
+                        const int v = 16 * t + lr + 4 * i;
+                        if (v < lv) colpart[(long long)v * colpart_stride + I * n + cb + lc] = o[i];
+                    }
                 }
             }
+        };
+        auto row_products = [&] {
+#pragma unroll
+            for (int t = 0; t < NVT; ++t)
+#pragma unroll
+                for (int jj = 0; jj < 4; ++jj)
+#pragma unroll
+                    for (int kb = 0; kb < 4; ++kb) {
+                        const double tv = mysh[(16 * jj + lc) * SMM_PITCH + 4 * kb + lr];
+                        dr[t][jj] = __builtin_amdgcn_mfma_f64_16x16x4f64(gc[t][kb], tv, dr[t][jj], 0, 0, 0);
+                    }
+        };
+        if constexpr (ROT) {  // x[] and bv[] are free: the next block's round trip runs behind the row products
+            __builtin_amdgcn_sched_barrier(0);
+            pl_drain_vmem();
+            store_colsums();  // ahead of the loads: whoever waits for the loads has waited for these
+            if (b + 4 < nblk) load_block(cb + 64);
+            __builtin_amdgcn_sched_barrier(0);
         }
+        row_products();
+        if constexpr (ROT) __builtin_amdgcn_sched_barrier(0);  // (the copies into the loop-carried x[] wait for the loads: not among the MFMAs)
+        else store_colsums();
+    }
+    };
+    if constexpr (ROT) {
+        if (prod) block_loop(PlConst<true>{});
+        else block_loop(PlConst<false>{});
+    } else {
+        block_loop(PlValue{prod});
     }
     if (!prod) return;
     __syncthreads();
@@ -1636,7 +1792,7 @@ __device__ __forceinline__ void apply_symm_tile(double* __restrict__ Q, long lon
     }
 }
 
-template <int NP, bool NT, int SEG, bool WIDE, bool PK = false>  // PK: gT = gP, colpart = colpart2, pendP as k_pack_operands leaves them
+template <int NP, bool NT, int SEG, bool WIDE, bool PK = false, int PL = APPLY_SYMM_PL>  // PK: gT = gP, colpart = colpart2, pendP as k_pack_operands leaves them
 __global__ __launch_bounds__(256, 2) void k_apply_symm_q(double* __restrict__ Q, long long ld, long long n,
                                                          const double* __restrict__ pend, const double* __restrict__ cpend,
                                                          const double* __restrict__ gT, int lv, double* __restrict__ rowpart,
@@ -1647,8 +1803,8 @@ __global__ __launch_bounds__(256, 2) void k_apply_symm_q(double* __restrict__ Q,
                                                          const double* __restrict__ pendP = nullptr) {
     static_assert(NP % 8 == 0, "k-steps taken in pairs");
     __shared__ double sh[4][SYMV_H * SMM_PITCH];
-    __shared__ double sgr[SYMV_H][SMM_NV2 + 1];
-    __shared__ double sa[SYMV_H * NP];
+    __shared__ alignas(16) double sgr[SYMV_H][SMM_NV2 + 1];
+    __shared__ alignas(16) double sa[SYMV_H * NP];
     __shared__ int s_t;
     const bool prod = !st->halted;  // (the update is owed either way)
     for (;;) {
@@ -1660,7 +1816,7 @@ __global__ __launch_bounds__(256, 2) void k_apply_symm_q(double* __restrict__ Q,
         __syncthreads();
         const int t = s_t;
         if (t < 0) return;  // (uniform)
-        apply_symm_tile<NP, NT, SEG, WIDE, PK>(Q, ld, n, (long long)tiles[t].I, (long long)tiles[t].J, pend, cpend, gT, lv, rowpart,
+        apply_symm_tile<NP, NT, SEG, WIDE, PK, PL>(Q, ld, n, (long long)tiles[t].I, (long long)tiles[t].J, pend, cpend, gT, lv, rowpart,
                                                colpart, rowpart_stride, colpart_stride, prod, sh, sgr, sa, pendP);
     }
 }
