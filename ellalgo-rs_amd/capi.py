@@ -130,6 +130,13 @@ BATCH_LMI_STREAMED_EXPORTS = [
     "ellhip_batch_lmi_optim_streamed_stable", "ellhip_batch_lmi_feas_streamed_stable",
 ]
 
+# every symbol include/ellhip_batch_maxcut.h declares (kept apart from EXPORTS, like SVM_EXPORTS)
+BATCH_MAXCUT_EXPORTS = [
+    "ellhip_batch_maxcut_create", "ellhip_batch_maxcut_destroy", "ellhip_batch_maxcut_set_chunk",
+    "ellhip_batch_maxcut_assess_optim", "ellhip_batch_maxcut_optim", "ellhip_batch_maxcut_optim_stable",
+    "ellhip_batch_maxcut_optim_streamed", "ellhip_batch_maxcut_optim_streamed_stable",
+]
+
 
 class EllHipError(RuntimeError):
     pass
@@ -397,11 +404,20 @@ def load():
         "ellhip_batch_lmi_feas_streamed": (i32, [vp, vp, i64, dbl, vp, vp, vp, vp]),
         "ellhip_batch_lmi_optim_streamed_stable": (i32, [vp, vp, vp, i64, dbl, vp, vp, vp, vp]),
         "ellhip_batch_lmi_feas_streamed_stable": (i32, [vp, vp, i64, dbl, vp, vp, vp, vp]),
+        # include/ellhip_batch_maxcut.h (the loops as ellhip_batch_svm_optim)
+        "ellhip_batch_maxcut_create": (i32, [C.POINTER(vp), i64, i64, vp, i32, i32]),
+        "ellhip_batch_maxcut_destroy": (None, [vp]),
+        "ellhip_batch_maxcut_set_chunk": (i32, [vp, i64]),
+        "ellhip_batch_maxcut_assess_optim": (i32, [vp, vp, vp, vp, vp, vp, vp]),
+        "ellhip_batch_maxcut_optim": (i32, [vp, vp, vp, i64, dbl, vp, vp, vp, vp]),
+        "ellhip_batch_maxcut_optim_stable": (i32, [vp, vp, vp, i64, dbl, vp, vp, vp, vp]),
+        "ellhip_batch_maxcut_optim_streamed": (i32, [vp, vp, vp, i64, dbl, vp, vp, vp, vp]),
+        "ellhip_batch_maxcut_optim_streamed_stable": (i32, [vp, vp, vp, i64, dbl, vp, vp, vp, vp]),
     }
     for name in (EXPORTS + SVM_EXPORTS + BATCH_LMI_EXPORTS + BATCH_LOWPASS_EXPORTS + BATCH_SVM_EXPORTS + LMI_LOOP_EXPORTS +
                  BATCH_STABLE_LOOP_EXPORTS + BATCH_STREAMED_EXPORTS + BATCH_LOWPASS_STREAMED_EXPORTS +
                  BATCH_STREAMED_STABLE_EXPORTS + BATCH_LOWPASS_STREAMED_STABLE_EXPORTS + BATCH_SVM_STREAMED_EXPORTS +
-                 BATCH_LMI_STREAMED_EXPORTS):
+                 BATCH_LMI_STREAMED_EXPORTS + BATCH_MAXCUT_EXPORTS):
         fn = getattr(L, name)  # AttributeError if the library does not export it
         fn.restype, fn.argtypes = sig[name]
     _lib = L
@@ -412,7 +428,7 @@ def batch_loop_entry(batch, name: str) -> str:
     """The entry point that runs loop `name` on `batch`: the Ell one, its `_stable` sibling
     (include/ellhip_batch_stable_loops.h) for an EllStableBatch, `_streamed` for an EllBatchStreamed and `_streamed_stable`
     for an EllStableBatchStreamed (include/ellhip_batch_{lmi,lowpass,svm}_streamed.h,
-    ellhip_batch_lowpass_streamed_stable.h).  A handle without an `is_streamed` attribute is not streamed."""
+    ellhip_batch_lowpass_streamed_stable.h, ellhip_batch_maxcut.h).  A handle without an `is_streamed` attribute is not streamed."""
     streamed = "_streamed" if getattr(batch, "is_streamed", False) else ""
     return name + streamed + ("_stable" if batch.variant == SPACE_ELL_STABLE else "")
 

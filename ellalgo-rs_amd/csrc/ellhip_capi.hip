@@ -2977,3 +2977,4 @@ int ellhip_profile_read(ellhip_space* s, double* ms_out, int64_t* count_out) {
 #include "batch_lowpass_streamed_stable_capi.inc.hpp"
 #include "batch_svm_streamed_capi.inc.hpp"
 #include "batch_lmi_streamed_capi.inc.hpp"
+#include "batch_maxcut_capi.inc.hpp"
