@@ -1161,9 +1161,11 @@ __device__ __forceinline__ void pk_stage_sgr(const double* __restrict__ gP, long
 //   PL_SGR2    the strip's A operands lie in LDS as pairs, sgr2[((t 8 + j2) 64 + lane) 2 + e] = gT[r0 + 4 (2 j2 + e) + lr][16 t + lc]:
 //              one 16-byte read per two column-product MFMAs (the same 16 KiB inside the same array);
 //   PL_ACC     fused pass: each of the four update accumulators takes all its k-steps back to back.
+// Measured piece by piece on MI355X at n = 16384 (profiles/r07/pass_pipeline.txt, section 3): the fused pass 660 us with none, 646
+// with PL_ROTATE, 627 with PL_SGR2 added, 627 with PL_ACC added (dispatch-to-dispatch spread 8 us) -- PL_ACC buys nothing and is off.
 constexpr int PL_ROTATE = 1, PL_SGR2 = 2, PL_ACC = 4;
 constexpr int SYMM2_PL = PL_ROTATE | PL_SGR2;
-constexpr int APPLY_SYMM_PL = PL_ROTATE | PL_SGR2 | PL_ACC;
+constexpr int APPLY_SYMM_PL = PL_ROTATE | PL_SGR2;
 // PL_ROTATE, ahead of the guarded loads of block b + 4: everything issued so far (this block's gc, its Q stores, the column sums of
 // block b - 4 -- all at least one product phase old) has returned.  The compiler counts vmcnt along the path WITHOUT the guarded
 // loads, so a wait for gc placed after them would wait for them as well; after this one the row products need none, and the

@@ -1703,6 +1703,16 @@ void multi_free(ellhip_space* s) {
 // first pass to its last stage: the option is read here only, and set between runs).  Row shards stay on the unpacked kernels.
 bool packed_on(const ellhip_space* s) { return s->packed_operands != 0 && !s->sharded && s->symm_ntiles > 0 && s->d_pendP != nullptr; }
 
+// Which form of k_group_reduce_p reads the column sums of a group of g cuts (group_kernels.hpp).  The pass has just written them:
+// the lower triangle of (g + 1) / 2 planes of 16 bytes per strip and column.  Up to about the 256 MiB of the Infinity Cache most of
+// them are still on the die and plain loads find them there (n = 16384: a group of 16 is 256 MiB, and non-temporal loads cost it
+// 15 us of 60); well beyond, they come from HBM and are read once: the streaming form (a group of 32: 129 us instead of 175).
+// Same bits either way.
+bool group_reduce_streams(const ellhip_space* s, int g) {
+    const double bytes = (double)((g + 1) / 2) * (double)colpart_elems(s) * 16.0 / 2.0;
+    return bytes > 1.5 * 256.0 * 1024.0 * 1024.0;
+}
+
 // the scalar stage of a group whose products sit in the partial-sum sets 2 .. 2 + g - 1 (group_kernels.hpp)
 // phase 0: the reductions (they read the pass' partial sums at HBM rate and want the whole card); phase 1: the rest (Gram slices,
 // sums, the one-wave recurrence, the vectors: short kernels that run beside the NEXT group's pass on the CU slots it leaves free)
@@ -1718,10 +1728,15 @@ int group_stage_go(ellhip_space* s, long long i, int g, int half, int phase) {
             hipLaunchKernelGGL(k_group_reduce<0>, dim3(nb, (unsigned)g), dim3(256), 0, s->stream, s->n, s->row0, s->nrows,
                                (long long)s->symv_seg, rowp, colp, (long long)rowpart_elems(s), (long long)colpart_elems(s),
                                s->d_grpY, grads, s->n, (const double*)s->d_pend, s->d_gpart, (const DevState*)s->d_st);
-        else if (packed_on(s))  // (the pass of this group stored its column sums in pairs)
-            hipLaunchKernelGGL(k_group_reduce_p<NP>, dim3(nb, (unsigned)(g + 1) / 2), dim3(256), 0, s->stream, s->n, s->row0, s->nrows,
-                               (long long)s->symv_seg, rowp, colp, (long long)rowpart_elems(s), (long long)colpart_elems(s),
-                               s->d_grpY, grads, s->n, (const double*)s->d_pend, s->d_gpart, (const DevState*)s->d_st, g, s->npend);
+        else if (packed_on(s)) {  // (the pass of this group stored its column sums in pairs)
+#define ELLHIP_REDUCE_P(PL)                                                                                                         \
+    hipLaunchKernelGGL((k_group_reduce_p<NP, PL>), dim3(nb, (unsigned)(g + 1) / 2), dim3(256), 0, s->stream, s->n, s->row0, s->nrows, \
+                       (long long)s->symv_seg, rowp, colp, (long long)rowpart_elems(s), (long long)colpart_elems(s), s->d_grpY,     \
+                       grads, s->n, (const double*)s->d_pend, s->d_gpart, (const DevState*)s->d_st, g, s->npend)
+            if (group_reduce_streams(s, g)) ELLHIP_REDUCE_P(GROUP_REDUCE_PL_STREAM);
+            else ELLHIP_REDUCE_P(GROUP_REDUCE_PL_CACHED);
+#undef ELLHIP_REDUCE_P
+        }
         else
             hipLaunchKernelGGL(k_group_reduce<NP>, dim3(nb, (unsigned)g), dim3(256), 0, s->stream, s->n, s->row0, s->nrows,
                                (long long)s->symv_seg, rowp, colp, (long long)rowpart_elems(s), (long long)colpart_elems(s),
@@ -1755,19 +1770,29 @@ int group_stage_go(ellhip_space* s, long long i, int g, int half, int phase) {
     return 0;
 }
 
+// The operands of a product pass: the gradients in the pass' order in half `half` of gT, and that half's tile counter rewound.  It
+// writes nothing else, and the last reader of both is the pass that ran on that half before.
+void symm_pack_go(ellhip_space* s, const double* g_dev, int lv, hipStream_t st, int half) {
+    double* gT = s->d_gT + (size_t)half * (size_t)s->n * MULTI_MAX;
+    unsigned* queue = s->d_symm_queue + 32 * half;
+    const int nvw = lv > SMM_NV ? SMM_NV2 : SMM_NV;  // one or two 16-wide column tiles
+    if (packed_on(s))
+        hipLaunchKernelGGL(k_pack_operands, dim3((unsigned)(s->n * (nvw / SMM_NV) / 32)), dim3(256), 0, st, g_dev, s->n, lv, s->n, gT, queue,
+                           nvw / SMM_NV, (const double*)nullptr, (double*)nullptr, 0);
+    else
+        hipLaunchKernelGGL(k_pack_grads, dim3((unsigned)((s->n * nvw + 255) / 256)), dim3(256), 0, st, g_dev, s->n, lv, s->n, gT, queue, nvw);
+}
+
+// packed: symm_pack_go for this group and half has been issued ahead of the pass already (queue_run_multi)
 template <int SEG>
-void symm_mfma_go(ellhip_space* s, const double* g_dev, int lv, hipStream_t st, int half, int wgs) {
+void symm_mfma_go(ellhip_space* s, const double* g_dev, int lv, hipStream_t st, int half, int wgs, bool packed) {
     double* gT = s->d_gT + (size_t)half * (size_t)s->n * MULTI_MAX;
     double* rowp = s->d_rowpart_m + (size_t)half * MULTI_MAX * rowpart_elems(s);
     double* colp = s->d_colpart_m + (size_t)half * MULTI_MAX * colpart_elems(s);
     unsigned* queue = s->d_symm_queue + 32 * half;
     const int nvw = lv > SMM_NV ? SMM_NV2 : SMM_NV;  // one or two 16-wide column tiles
     const bool pk = packed_on(s);
-    if (pk)
-        hipLaunchKernelGGL(k_pack_operands, dim3((unsigned)(s->n * (nvw / SMM_NV) / 32)), dim3(256), 0, st, g_dev, s->n, lv, s->n, gT, queue,
-                           nvw / SMM_NV, (const double*)nullptr, (double*)nullptr, 0);
-    else
-        hipLaunchKernelGGL(k_pack_grads, dim3((unsigned)((s->n * nvw + 255) / 256)), dim3(256), 0, st, g_dev, s->n, lv, s->n, gT, queue, nvw);
+    if (!packed) symm_pack_go(s, g_dev, lv, st, half);
     const bool nt = s->sh_gemv.nt != 0;
 #define ELLHIP_SYMM_Q(...)                                                                                                          \
     hipLaunchKernelGGL((__VA_ARGS__), dim3((unsigned)wgs), dim3(256), 0, st, (const double*)s->d_Q, s->ld, s->n, s->row0,                \
@@ -1878,11 +1903,11 @@ long long group_size(const ellhip_space* s, long long cap, long long rem) {
 // beside: the pass is issued next to the previous group's stage -- it leaves a sixteenth of its workgroup slots free, where that
 // stage's short kernels run (a pass that draws its tiles from a queue keeps every slot it gets until it ends; with a 32nd free
 // k_group_sums did not get on the card before the pass ended, with an eighth the pass itself lost more than the stage gained)
-int symm_go(ellhip_space* s, const double* g_dev, int lv, hipStream_t st, int half, bool beside = false) {
+int symm_go(ellhip_space* s, const double* g_dev, int lv, hipStream_t st, int half, bool beside = false, bool packed = false) {
     ProfScope ps(s, CLS_SYMV, st);
     const int wgs = beside ? std::max(1, s->symm_wgs - std::max(1, s->symm_wgs / 16)) : s->symm_wgs;
-    if (s->symv_seg == SYMV_SEG) symm_mfma_go<SYMV_SEG>(s, g_dev, lv, st, half, wgs);
-    else symm_mfma_go<SYMV_SEG_SMALL>(s, g_dev, lv, st, half, wgs);
+    if (s->symv_seg == SYMV_SEG) symm_mfma_go<SYMV_SEG>(s, g_dev, lv, st, half, wgs, packed);
+    else symm_mfma_go<SYMV_SEG_SMALL>(s, g_dev, lv, st, half, wgs, packed);
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -1986,13 +2011,26 @@ int queue_run_multi(ellhip_space* s, long long first, long long count) {
     (qdepth == MAXPEND ? group_stage_go<MAXPEND>(s, i, (int)g, half, PHASE)                                          \
      : qdepth == 24    ? group_stage_go<24>(s, i, (int)g, half, PHASE)                                               \
      : qdepth == 16    ? group_stage_go<16>(s, i, (int)g, half, PHASE) : group_stage_go<8>(s, i, (int)g, half, PHASE))
+            // (the NEXT group's operands first, on the second stream: they go into the other half of gT and rewind its tile counter,
+            // whose last reader is the pass that ran on that half one group earlier -- enqueued on, or joined into, the handle's
+            // stream by now, so the fork covers it.  Only the pass itself waits for the reductions.)
+            const bool go_side = use_side && g2 >= 2;
+            if (go_side) {
+                rc = side_fork(s);
+                if (rc) return rc;
+                symm_pack_go(s, qgrad(s, i2), (int)g2, side_stream(s), half ^ 1);
+                HIPCHK(hipGetLastError());
+            }
             rc = ELLHIP_STAGE(0);
-            if (rc) return rc;
+            if (rc) {
+                if (go_side) (void)side_mark(s);  // (the operands' launch is side work in flight: the guard joins it)
+                return rc;
+            }
             // ... then the NEXT group's products on the second stream, behind those reductions and beside the rest of this
             // stage (short kernels, one of them a single wave: they run on the slots the pass leaves free)
-            if (use_side && g2 >= 2) {
+            if (go_side) {
                 rc = side_fork(s);  // after this group's reductions: the last reader of the other half, every writer of Q so far
-                if (!rc) rc = symm_go(s, qgrad(s, i2), (int)g2, side_stream(s), half ^ 1, true);
+                if (!rc) rc = symm_go(s, qgrad(s, i2), (int)g2, side_stream(s), half ^ 1, true, true);
                 if (!rc) rc = side_mark(s);
                 if (rc) return rc;
                 ahead_i = i2;

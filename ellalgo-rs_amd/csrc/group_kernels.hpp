@@ -18,6 +18,7 @@
 #pragma once
 
 #include "ell_kernels.hpp"
+#include "group_reduce_map.hpp"
 
 namespace ellhip {
 
@@ -49,7 +50,7 @@ __global__ __launch_bounds__(256) void k_group_reduce(long long n, long long row
 }
 
 // ELLHIP_OPT_PACKED_OPERANDS: the same from the packed passes' column sums, colpart2[p][I][c][2] = those of cuts 2 p, 2 p + 1
-// side by side (ell_kernels.hpp, k_pack_operands).  One workgroup per pair (grid.y = p) and 128 columns; every addition of
+// side by side (ell_kernels.hpp, k_pack_operands).  One workgroup per pair and 128 columns; every addition of
 // symv_reduce_block<NP, false> is made in its order, so Y and gpart are word for word what k_group_reduce writes:
 //   - column sums: lane L of wave w takes columns 128 blk + L and 128 blk + 64 + L of both cuts (16-byte loads, 1 KiB per
 //     wave-instruction), each from its own first strip I0(c) + w in steps of four, and leaves the four sums in LDS;
@@ -57,7 +58,28 @@ __global__ __launch_bounds__(256) void k_group_reduce(long long n, long long row
 //     + ((c0 + c1) + c2) + c3, y, g.y;
 //   - v_j.g: wave w takes j = w, w + 4, ... for both cuts (one load of v_j serves the two).
 // Unsharded handles (the dot products are formed here).  G = cuts of the group: an odd group's last pair has one.
-template <int NP>
+// PL: how the bytes arrive, a mask of three pieces -- the additions, their order and the output addressing are the same for every
+// PL, so Y and gpart are word for word the same (tests/cpp/group_reduce_check.hip compares the shipped forms against PL = 0):
+//   0          grid (blk, p); plain loads; the two 64-column halves one after the other, each with a 16-wide, an 8-wide and a
+//              1-wide strip loop;
+//   RED_LOOP   ONE strip loop per lane that requests 16 strips of BOTH halves before the first addition (32 x 16 bytes in flight
+//              per lane, no drain between the halves), and whose last trip is the same wide trip, clamped and predicated: a strip
+//              past the last one is loaded from the last strip's (valid) address and enters the sum as +0.0.  Each half keeps its
+//              own running sum in the same u order.  A running sum starts at +0.0 and x + y is -0.0 only when both are -0.0, so no
+//              running sum is ever -0.0, and s + (+0.0) == s bit for bit for every other s (NaN included): the trailing additions
+//              change nothing;
+//   RED_NT     the partial sums -- read exactly once -- come through non-temporal loads;
+//   RED_HEAVY  the launch goes from the heavy column blocks to the light ones across the pairs (group_reduce_map.hpp).
+// Two forms ship, chosen per launch by what the reduction reads (group_reduce_streams, ellhip_capi.hip; MI355X, n = 16384, medians
+// of 16 dispatches inside queue runs, dispatch-to-dispatch spread 2-3 us, profiles/r08/):
+//   the sums of a group of 32 (2 x the Infinity Cache) come from HBM        0: 178   LOOP: 175   LOOP | NT: 129   all three: 137 us
+//   those of a group of 16 (written a moment ago, = the Infinity Cache)    0: 69    LOOP: 63    LOOP | HEAVY: 60   LOOP | NT: 78
+// Non-temporal loads are worth a quarter of the time on a stream from HBM and cost a seventh where the plain loads still find
+// most lines on the die; heavy first pays only there (with non-temporal loads it costs 8 us at either size).
+constexpr int RED_LOOP = 1, RED_NT = 2, RED_HEAVY = 4;
+constexpr int GROUP_REDUCE_PL_STREAM = RED_LOOP | RED_NT;     // partial sums that no longer fit the Infinity Cache
+constexpr int GROUP_REDUCE_PL_CACHED = RED_LOOP | RED_HEAVY;  // partial sums that mostly still sit in it
+template <int NP, int PL = GROUP_REDUCE_PL_STREAM>
 __global__ __launch_bounds__(256) void k_group_reduce_p(long long n, long long row0, long long nrows, long long seg,
                                                         const double* __restrict__ rowpart,
                                                         const double* __restrict__ colpart2, long long rowpart_stride,
@@ -66,10 +88,13 @@ __global__ __launch_bounds__(256) void k_group_reduce_p(long long n, long long r
                                                         const double* __restrict__ pend, double* __restrict__ gpart,
                                                         const DevState* __restrict__ st, int G, int slot0 = NP) {
     static_assert(NP > 0, "row shards keep k_group_reduce<0>");
+    constexpr bool NT = (PL & RED_NT) != 0;  // (rowpart and colpart2 only: pend and g are read again by the next kernels)
     __shared__ alignas(16) double part[2][4][128];  // [cut of the pair][wave][column of the block]
     if (st->halted) return;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const long long p = blockIdx.y, nb = gridDim.x, blk = blockIdx.x;
+    const long long nb = gridDim.x;
+    long long blk, p;
+    group_reduce_slot((PL & RED_HEAVY) != 0, blockIdx.x, blockIdx.y, gridDim.x, gridDim.y, blk, p);
     const long long i = blk * 128 + 2 * lane;  // the old map's column pair
     const long long nstrips = (nrows + SYMV_H - 1) / SYMV_H;
     const bool two = 2 * p + 1 < G;
@@ -87,40 +112,78 @@ __global__ __launch_bounds__(256) void k_group_reduce_p(long long n, long long r
         pv[k] = (i < n && j < NP && j < slot0) ? *reinterpret_cast<const double2_t*>(pend + (long long)j * n + i) : double2_t{0.0, 0.0};
     }
     const double* cp = colpart2 + 2 * p * colpart_stride;
+    if constexpr ((PL & RED_LOOP) == 0) {
 #pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        const long long c = blk * 128 + 64 * h + lane;
-        double2_t s = {0.0, 0.0};  // .x: cut 2 p, .y: cut 2 p + 1
-        if (c < n) {
-            long long I = (c < row0 ? 0 : (c - row0) / SYMV_H) + wave;
-            for (; I + 60 < nstrips; I += 64) {
-                double2_t v[16];
+        for (int h = 0; h < 2; ++h) {
+            const long long c = blk * 128 + 64 * h + lane;
+            double2_t s = {0.0, 0.0};  // .x: cut 2 p, .y: cut 2 p + 1
+            if (c < n) {
+                long long I = (c < row0 ? 0 : (c - row0) / SYMV_H) + wave;
+                for (; I + 60 < nstrips; I += 64) {
+                    double2_t v[16];
 #pragma unroll
-                for (int u = 0; u < 16; ++u) v[u] = *reinterpret_cast<const double2_t*>(cp + 2 * ((I + 4 * u) * n + c));
+                    for (int u = 0; u < 16; ++u) v[u] = ld_stream<NT, double2_t>(cp + 2 * ((I + 4 * u) * n + c));
 #pragma unroll
-                for (int u = 0; u < 16; ++u) {
-                    s.x += v[u].x;
-                    s.y += v[u].y;
+                    for (int u = 0; u < 16; ++u) {
+                        s.x += v[u].x;
+                        s.y += v[u].y;
+                    }
+                }
+                for (; I + 28 < nstrips; I += 32) {
+                    double2_t v[8];
+#pragma unroll
+                    for (int u = 0; u < 8; ++u) v[u] = ld_stream<NT, double2_t>(cp + 2 * ((I + 4 * u) * n + c));
+#pragma unroll
+                    for (int u = 0; u < 8; ++u) {
+                        s.x += v[u].x;
+                        s.y += v[u].y;
+                    }
+                }
+                for (; I < nstrips; I += 4) {
+                    const double2_t v = ld_stream<NT, double2_t>(cp + 2 * (I * n + c));
+                    s.x += v.x;
+                    s.y += v.y;
                 }
             }
-            for (; I + 28 < nstrips; I += 32) {
-                double2_t v[8];
+            part[0][wave][64 * h + lane] = s.x;
+            part[1][wave][64 * h + lane] = s.y;
+        }
+    } else {
+        // halves 0 and 1 = columns c0 and c1; a column past n has no strips (I = nstrips) and borrows a valid column for its addresses
+        const long long c0 = blk * 128 + lane, c1 = c0 + 64;
+        const long long a0 = c0 < n ? c0 : n - 1, a1 = c1 < n ? c1 : a0;
+        long long I0 = c0 < n ? (c0 < row0 ? 0 : (c0 - row0) / SYMV_H) + wave : nstrips;
+        long long I1 = c1 < n ? (c1 < row0 ? 0 : (c1 - row0) / SYMV_H) + wave : nstrips;
+        double2_t s0 = {0.0, 0.0}, s1 = {0.0, 0.0};  // .x: cut 2 p, .y: cut 2 p + 1
+        const double* b0 = cp + 2 * a0;
+        const double* b1 = cp + 2 * a1;
+        for (; I0 < nstrips; I0 += 64, I1 += 64) {  // (I0 <= I1: half 1 never has more trips)
+            double2_t v0[16], v1[16];
 #pragma unroll
-                for (int u = 0; u < 8; ++u) v[u] = *reinterpret_cast<const double2_t*>(cp + 2 * ((I + 4 * u) * n + c));
-#pragma unroll
-                for (int u = 0; u < 8; ++u) {
-                    s.x += v[u].x;
-                    s.y += v[u].y;
-                }
+            for (int u = 0; u < 16; ++u) {
+                const long long Iu = I0 + 4 * u < nstrips ? I0 + 4 * u : nstrips - 1;
+                v0[u] = ld_stream<NT, double2_t>(b0 + 2 * Iu * n);
             }
-            for (; I < nstrips; I += 4) {
-                const double2_t v = *reinterpret_cast<const double2_t*>(cp + 2 * (I * n + c));
-                s.x += v.x;
-                s.y += v.y;
+#pragma unroll
+            for (int u = 0; u < 16; ++u) {
+                const long long Iu = I1 + 4 * u < nstrips ? I1 + 4 * u : nstrips - 1;
+                v1[u] = ld_stream<NT, double2_t>(b1 + 2 * Iu * n);
+            }
+#pragma unroll
+            for (int u = 0; u < 16; ++u) {
+                s0.x += (I0 + 4 * u < nstrips) ? v0[u].x : 0.0;
+                s0.y += (I0 + 4 * u < nstrips) ? v0[u].y : 0.0;
+            }
+#pragma unroll
+            for (int u = 0; u < 16; ++u) {
+                s1.x += (I1 + 4 * u < nstrips) ? v1[u].x : 0.0;
+                s1.y += (I1 + 4 * u < nstrips) ? v1[u].y : 0.0;
             }
         }
-        part[0][wave][64 * h + lane] = s.x;
-        part[1][wave][64 * h + lane] = s.y;
+        part[0][wave][lane] = s0.x;
+        part[1][wave][lane] = s0.y;
+        part[0][wave][64 + lane] = s1.x;
+        part[1][wave][64 + lane] = s1.y;
     }
     // row partial sums of this wave's cut (waves 0 and 1), requested before the barrier, added in segment order
     const bool fin = wave == 0 || (wave == 1 && two);
@@ -134,7 +197,7 @@ __global__ __launch_bounds__(256) void k_group_reduce_p(long long n, long long r
 #pragma unroll
             for (int u = 0; u < 8; ++u) {
                 const long long Ju = (J + u < nJ) ? J + u : nJ - 1;
-                v[u] = *reinterpret_cast<const double2_t*>(rp + Ju * n + i);
+                v[u] = ld_stream<NT, double2_t>(rp + Ju * n + i);
             }
 #pragma unroll
             for (int u = 0; u < 8; ++u) {
