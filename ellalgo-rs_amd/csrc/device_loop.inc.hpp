@@ -1,6 +1,6 @@
 // device_loop.inc.hpp -- the device-resident cutting-plane loop shared by the device-side oracles (lowpass_capi.inc.hpp,
 // svm_capi.inc.hpp).  Included by them inside the one translation unit of ellhip_capi.hip: it issues the search-space
-// primitives do_prime / do_cut / do_commit directly.
+// primitives do_prime / do_cut / do_commit (ell_primitives_capi.inc.hpp) directly.
 //
 // Reference: src/cutting_plane.rs:205-227,286-313.  The host enqueues iterations in batches of DL_BATCH; every kernel of
 // an iteration (the oracle's, GEMV, scalar stage, shrink) is a no-op once the loop has halted on the device, so the host

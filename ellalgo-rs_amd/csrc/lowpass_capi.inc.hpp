@@ -1,6 +1,6 @@
 // lowpass_capi.inc.hpp -- C ABI of the device-side LowpassOracle and of the device-resident
 // cutting-plane loops built on it.  Included at the end of ellhip_capi.hip (same translation unit: it
-// issues the search-space primitives do_prime / do_cut / do_commit directly).
+// issues the search-space primitives do_prime / do_cut / do_commit of ell_primitives_capi.inc.hpp directly).
 //
 // Reference: src/oracles/lowpass_oracle.rs:22-151 (oracle), src/cutting_plane.rs:205-227,286-313 (loops).
 #include "../../include/ellhip_lowpass.h"

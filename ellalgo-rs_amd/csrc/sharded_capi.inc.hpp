@@ -1,4 +1,5 @@
-// sharded_capi.inc.hpp -- implementation of include/ellhip_sharded.h (included at the end of ellhip_capi.hip).
+// sharded_capi.inc.hpp -- implementation of include/ellhip_sharded.h (included at the end of ellhip_capi.hip;
+// it drives shard handles through ell_queue_capi.inc.hpp and, for a symmetric shard's group runs, ell_group_capi.inc.hpp).
 //
 // One process per GPU; this rank's row block is an ordinary shard handle (ellhip_create_shard) and the ONE collective
 // of an update is issued by the library on the handle's stream through RCCL, which is opened at run time (dlopen), so

@@ -1,5 +1,5 @@
 // svm_capi.inc.hpp -- C ABI of the device-side SvmOracle and of the device-resident cutting-plane loop built on it.
-// Included at the end of ellhip_capi.hip (same translation unit: the loop issues the search-space primitives directly).
+// Included at the end of ellhip_capi.hip (same translation unit: the loop issues the primitives of ell_primitives_capi.inc.hpp directly).
 //
 // Reference: src/oracles/svm_oracle.rs:4-58 (oracle), src/cutting_plane.rs:286-313 (loop).
 #include "../../include/ellhip_svm.h"

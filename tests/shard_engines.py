@@ -40,7 +40,7 @@ class OracleShardEngine:
     def set_defer_depth(self, depth):
         self._observer()
 
-    # ---- the three primitives (mirror of prime / cut / commit in csrc/ellhip_capi.hip)
+    # ---- the three primitives (mirror of prime / cut / commit in csrc/ell_primitives_capi.inc.hpp)
     def _gemv(self, g):
         if not self.symmetric:
             oracle.rows_gemv(self.n, self.row0, self.nrows, self.Q, g, self.gt_np)

@@ -1,5 +1,5 @@
 """CPU: bench.py's byte models (no GPU, no engine): the passes over Q a pipelined queue run makes with the queue's
-lookahead (csrc/ellhip_capi.hip queue_run_multi groups the cuts the same way) and the per-update byte counts the JSON line
+lookahead (csrc/ell_group_capi.inc.hpp queue_run_multi groups the cuts the same way) and the per-update byte counts the JSON line
 carries.  Reference quantities: one update = src/ell.rs:97-137 (GEMV 8 n^2 + rank-1 16 n^2 bytes in its own data flow)."""
 import importlib.util
 import os

@@ -15,7 +15,7 @@ import stable_step_check as ssc
 from util import TOL, assert_state_close, beta_of, rel_inf, set_default
 
 pytestmark = pytest.mark.gpu
-PERIOD = 256   # ST_MIRROR_PERIOD (csrc/ellhip_capi.hip)
+PERIOD = 256   # ST_MIRROR_PERIOD (csrc/ellstable_capi.inc.hpp)
 
 
 def _handle(gpu, seq):

@@ -1,7 +1,7 @@
 """GPU: pipelined queue runs on the lower-triangle schedule that use what a QUEUE knows -- the next gradients.
 The GEMV y = Q_base g of a queued cut reads a matrix the cuts before it do not change until the next apply pass (recorded
 schedule: src/ell.rs:117-128 is deferred), so
-  * ELLHIP_OPT_LOOKAHEAD = L (default 32; csrc/ellhip_capi.hip queue_run_multi): the products of L consecutive queued cuts
+  * ELLHIP_OPT_LOOKAHEAD = L (default 32; csrc/ell_group_capi.inc.hpp queue_run_multi): the products of L consecutive queued cuts
     are formed in ONE pass over the lower triangle -- L <= 3 on the vector ALU (k_symv_multi, per vector k_symv's
     arithmetic), L > 3 on the FP64 matrix cores (k_symm_mfma, n a multiple of 64; own association: a few ulp) with the
     group's scalar stage in four launches (group_kernels.hpp) and, at depth 24, up to ELLHIP_OPT_QUEUE_DEPTH = 48

@@ -351,7 +351,7 @@ int main(int argc, char** argv) {
     const double tri = 4.0 * (double)n * (double)n;
 
     std::vector<Variant> vs;
-    // the unit list exactly as csrc/ellhip_capi.hip (symv_alloc) builds it
+    // the unit list exactly as csrc/ell_passes_capi.inc.hpp (symv_alloc) builds it
     std::vector<int4> units;
     {
         const long long seg = SYMV_SEG, nstrips = n / SYMV_H;
