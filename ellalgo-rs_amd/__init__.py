@@ -10,6 +10,7 @@ from .batch import EllBatch, EllBatchStreamed, EllStableBatch, EllStableBatchStr
 from .batch_lmi import BatchLmiProblem  # noqa: F401
 from .batch_lowpass import BatchLowpassProblem  # noqa: F401
 from .batch_maxcut import BatchMaxcutProblem  # noqa: F401
+from .batch_profit import BatchProfitProblem, math_eval  # noqa: F401
 from .batch_svm import BatchSvmProblem  # noqa: F401
 from .lmi import LDLTMgr, LMI0Oracle, LMIOracle  # noqa: F401
 from .lmi_loop import LmiLoopProblem  # noqa: F401
@@ -18,5 +19,5 @@ from .sharded_abi import ShardedEllAbi  # noqa: F401
 from .svm import SvmOracle  # noqa: F401
 
 __all__ = ["build", "capi", "synth", "CutStatus", "Ell", "EllStable", "ParallelCut", "SingleCut", "calc",
-           "EllBatch", "EllBatchStreamed", "EllStableBatch", "EllStableBatchStreamed", "BatchLmiProblem", "BatchLowpassProblem", "BatchMaxcutProblem", "BatchSvmProblem", "LDLTMgr", "LMIOracle", "LMI0Oracle", "LmiLoopProblem", "LowpassOracle", "create_lowpass_case", "lowpass_case_constants",
+           "EllBatch", "EllBatchStreamed", "EllStableBatch", "EllStableBatchStreamed", "BatchLmiProblem", "BatchLowpassProblem", "BatchMaxcutProblem", "BatchProfitProblem", "BatchSvmProblem", "LDLTMgr", "LMIOracle", "LMI0Oracle", "LmiLoopProblem", "LowpassOracle", "create_lowpass_case", "lowpass_case_constants",
            "SvmOracle"]

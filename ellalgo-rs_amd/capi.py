@@ -137,6 +137,15 @@ BATCH_MAXCUT_EXPORTS = [
     "ellhip_batch_maxcut_optim_streamed", "ellhip_batch_maxcut_optim_streamed_stable",
 ]
 
+# every symbol include/ellhip_batch_profit.h declares (kept apart from EXPORTS, like SVM_EXPORTS)
+BATCH_PROFIT_EXPORTS = [
+    "ellhip_batch_profit_create", "ellhip_batch_profit_destroy", "ellhip_batch_profit_set_chunk",
+    "ellhip_batch_profit_assess_optim", "ellhip_batch_profit_assess_optim_q", "ellhip_batch_profit_optim",
+    "ellhip_batch_profit_optim_stable", "ellhip_batch_profit_optim_q", "ellhip_batch_profit_optim_q_stable",
+    "ellhip_math_eval",
+]
+PROFIT_PLAIN, PROFIT_ROBUST, PROFIT_DISCRETE = 0, 1, 2
+
 
 class EllHipError(RuntimeError):
     pass
@@ -413,11 +422,22 @@ def load():
         "ellhip_batch_maxcut_optim_stable": (i32, [vp, vp, vp, i64, dbl, vp, vp, vp, vp]),
         "ellhip_batch_maxcut_optim_streamed": (i32, [vp, vp, vp, i64, dbl, vp, vp, vp, vp]),
         "ellhip_batch_maxcut_optim_streamed_stable": (i32, [vp, vp, vp, i64, dbl, vp, vp, vp, vp]),
+        # include/ellhip_batch_profit.h (the loops as ellhip_batch_maxcut_optim)
+        "ellhip_batch_profit_create": (i32, [C.POINTER(vp), i64, i32, vp, vp, vp, vp, i32]),
+        "ellhip_batch_profit_destroy": (None, [vp]),
+        "ellhip_batch_profit_set_chunk": (i32, [vp, i64]),
+        "ellhip_batch_profit_assess_optim": (i32, [vp, vp, vp, vp, vp, vp]),
+        "ellhip_batch_profit_assess_optim_q": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "ellhip_batch_profit_optim": (i32, [vp, vp, vp, i64, dbl, vp, vp, vp, vp]),
+        "ellhip_batch_profit_optim_stable": (i32, [vp, vp, vp, i64, dbl, vp, vp, vp, vp]),
+        "ellhip_batch_profit_optim_q": (i32, [vp, vp, vp, i64, dbl, vp, vp, vp, vp]),
+        "ellhip_batch_profit_optim_q_stable": (i32, [vp, vp, vp, i64, dbl, vp, vp, vp, vp]),
+        "ellhip_math_eval": (i32, [i32, i64, vp, vp, i32]),
     }
     for name in (EXPORTS + SVM_EXPORTS + BATCH_LMI_EXPORTS + BATCH_LOWPASS_EXPORTS + BATCH_SVM_EXPORTS + LMI_LOOP_EXPORTS +
                  BATCH_STABLE_LOOP_EXPORTS + BATCH_STREAMED_EXPORTS + BATCH_LOWPASS_STREAMED_EXPORTS +
                  BATCH_STREAMED_STABLE_EXPORTS + BATCH_LOWPASS_STREAMED_STABLE_EXPORTS + BATCH_SVM_STREAMED_EXPORTS +
-                 BATCH_LMI_STREAMED_EXPORTS + BATCH_MAXCUT_EXPORTS):
+                 BATCH_LMI_STREAMED_EXPORTS + BATCH_MAXCUT_EXPORTS + BATCH_PROFIT_EXPORTS):
         fn = getattr(L, name)  # AttributeError if the library does not export it
         fn.restype, fn.argtypes = sig[name]
     _lib = L

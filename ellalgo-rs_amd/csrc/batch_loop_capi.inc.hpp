@@ -6,7 +6,7 @@
 // batch_streamed_stable_capi.inc.hpp (it drives the batch engines' handle directly) and before every batch_*_capi.inc.hpp
 // of an oracle.
 //
-// Reference: src/cutting_plane.rs:205-227, 286-313 (loops).
+// Reference: src/cutting_plane.rs:205-227, 286-313, 331-374 (loops).
 #include "batch_loop_kernels.hpp"
 #include "batch_streamed_loop_kernels.hpp"
 #include "batch_streamed_stable_loop_kernels.hpp"
@@ -172,10 +172,10 @@ int batch_loop_check(const ellhip_batch* s, BatchLoopEngine e, const std::string
                                                           : "EllStable batch handles are not supported")).c_str());
 }
 
-template <int T, bool STABLE, class Oracle>
+template <int T, bool STABLE, class Oracle, int DRIVER = BATCH_DRIVER_OPTIM>
 int batch_loop_launch(const ellhip_batch* s, const BatchLoopShape& sh, size_t lds, const BatchLoopRun& R,
                       const BatchLoopState& S, const typename Oracle::Args& A, const EllCalcDev& calc) {
-    if (const int rc = batch_loop_allow_lds<&k_batch_loop<T, STABLE, Oracle>>(s->device, lds)) return rc;
+    if (const int rc = batch_loop_allow_lds<&k_batch_loop<T, STABLE, Oracle, DRIVER>>(s->device, lds)) return rc;
     BatchParams P;
     P.B = s->B;
     P.n = s->n;
@@ -184,7 +184,7 @@ int batch_loop_launch(const ellhip_batch* s, const BatchLoopShape& sh, size_t ld
     P.K = 0;
     P.no_defer_trick = s->no_defer_trick;
     const unsigned grid = (unsigned)((s->B + sh.epw - 1) / sh.epw);
-    hipLaunchKernelGGL((k_batch_loop<T, STABLE, Oracle>), dim3(grid), dim3(T), lds, s->stream, P, R, s->d_Q, s->d_xc,
+    hipLaunchKernelGGL((k_batch_loop<T, STABLE, Oracle, DRIVER>), dim3(grid), dim3(T), lds, s->stream, P, R, s->d_Q, s->d_xc,
                        s->d_kappa, s->d_tsq, S, A, calc);
     return 0;
 }
@@ -214,10 +214,11 @@ int batch_streamed_loop_launch(const ellhip_batch* s, size_t lds, const BatchLoo
 // The part of a run that does not depend on the kernel: cutting_plane_optim (feas = 0, gamma in and out) or
 // cutting_plane_feas for every instance, up to max_iters rounds in launches of st.chunk until every instance has stopped,
 // then the results.  launch(R) enqueues one launch of R.iters rounds on s->stream and returns 0 or an error code.  The
-// caller has checked that the spaces and the oracle fit each other.
+// caller has checked that the spaces and the oracle fit each other.  d_retry: the optim_q driver's retry flags [B], part of
+// the oracle's state in HBM and false when a run begins (src/cutting_plane.rs:343); null for the other drivers.
 template <class Launch>
 int batch_loop_drive(ellhip_batch* s, BatchLoopBuffers& st, int feas, double* gamma_inout, int64_t max_iters, double tol,
-                     double* x_out, int32_t* has_out, int64_t* niter_out, int32_t* status_out, Launch launch) {
+                     double* x_out, int32_t* has_out, int64_t* niter_out, int32_t* status_out, int* d_retry, Launch launch) {
     if (max_iters < 0) return fail(ELLHIP_E_INVALID, "max_iters must be >= 0");
     const size_t B = (size_t)st.B, n = (size_t)st.n;
     DeviceGuard guard(s->device);
@@ -225,6 +226,7 @@ int batch_loop_drive(ellhip_batch* s, BatchLoopBuffers& st, int feas, double* ga
     HIPCHK(hipStreamSynchronize(s->stream));
     HIPCHK(hipStreamSynchronize(st.stream));
     HIPCHK(batch_loop_reset(st, s->stream));
+    if (d_retry) HIPCHK(fill_now(d_retry, 0, B * sizeof(int), s->stream));
     if (!feas) HIPCHK(hipMemcpy(st.d_gamma, gamma_inout, B * sizeof(double), hipMemcpyHostToDevice));
     BatchLoopRun R;
     R.feas = feas;
@@ -259,36 +261,45 @@ int batch_loop_drive(ellhip_batch* s, BatchLoopBuffers& st, int feas, double* ga
 }
 
 // The loops of one oracle on one engine: the loop kernel of `engine` over a batch handle of that engine's kind.  The caller
-// has checked its pointers.
-template <class Oracle>
+// has checked its pointers.  DRIVER: which of the reference's drivers (batch_loop_kernels.hpp); the optim_q driver takes the
+// oracle's retry flags in d_retry.  STREAMED = false: an oracle that has the LDS engines' loop kernels only (the streamed
+// ones are then not built for it, and a streamed engine is refused).
+template <class Oracle, int DRIVER = BATCH_DRIVER_OPTIM, bool STREAMED = true>
 int batch_loop_run(ellhip_batch* s, BatchLoopBuffers& st, const typename Oracle::Args& A, const BatchLoopWords& w,
                    BatchLoopEngine engine, int feas, double* gamma_inout, int64_t max_iters, double tol, double* x_out,
-                   int32_t* has_out, int64_t* niter_out, int32_t* status_out) {
+                   int32_t* has_out, int64_t* niter_out, int32_t* status_out, int* d_retry = nullptr) {
+    static_assert(DRIVER == BATCH_DRIVER_OPTIM || !STREAMED, "the streamed loop kernels have no optim_q driver");
     const std::string what = batch_loop_what(w.oracle, engine);
+    if (!STREAMED && engine.streamed) return fail(ELLHIP_E_INVALID, (what + ": there is no streamed form of this loop").c_str());
     if (const int rc = batch_loop_check(s, engine, what)) return rc;
     if (s->B != st.B || s->n != st.n)
         return fail(ELLHIP_E_INVALID, (what + ": spaces and oracle differ in B or n" + w.n_is).c_str());
     if (s->device != st.device) return fail(ELLHIP_E_INVALID, (what + ": spaces and oracle live on different devices").c_str());
     const BatchLoopShape sh = engine.streamed ? BatchLoopShape{} : batch_loop_shape(s, engine.stable);  // the LDS engine's
-    const size_t doubles = !engine.streamed ? (size_t)sh.epw * (sh.space_doubles + Oracle::lds_doubles(A, s->n))
-                           : engine.stable  ? batch_streamed_stable_loop_lds_doubles<Oracle>(A, s->n)
-                                            : batch_streamed_loop_lds_doubles<Oracle>(A, s->n);
+    size_t doubles = (size_t)sh.epw * (sh.space_doubles + Oracle::lds_doubles(A, s->n));
+    if constexpr (STREAMED) {
+        if (engine.streamed)
+            doubles = engine.stable ? batch_streamed_stable_loop_lds_doubles<Oracle>(A, s->n)
+                                    : batch_streamed_loop_lds_doubles<Oracle>(A, s->n);
+    }
     const size_t lds = doubles * sizeof(double);
     if (lds > BATCH_LOOP_LDS_MAX)
         return fail(ELLHIP_E_INVALID, (what + ": this " + w.shape + " needs more LDS than a workgroup has").c_str());
     const EllCalcDev calc = EllCalcDev::make(s->n, s->use_parallel_cut);
     const BatchLoopState S = batch_loop_view(st);
-    return batch_loop_drive(s, st, feas, gamma_inout, max_iters, tol, x_out, has_out, niter_out, status_out,
+    return batch_loop_drive(s, st, feas, gamma_inout, max_iters, tol, x_out, has_out, niter_out, status_out, d_retry,
                             [&](const BatchLoopRun& R) {
-        if (engine.streamed)
-            return engine.stable ? batch_streamed_loop_launch<true, Oracle>(s, lds, R, S, A, calc)
-                                 : batch_streamed_loop_launch<false, Oracle>(s, lds, R, S, A, calc);
+        if constexpr (STREAMED) {
+            if (engine.streamed)
+                return engine.stable ? batch_streamed_loop_launch<true, Oracle>(s, lds, R, S, A, calc)
+                                     : batch_streamed_loop_launch<false, Oracle>(s, lds, R, S, A, calc);
+        }
         if (engine.stable)
-            return sh.T == 128 ? batch_loop_launch<128, true, Oracle>(s, sh, lds, R, S, A, calc)
-                               : batch_loop_launch<256, true, Oracle>(s, sh, lds, R, S, A, calc);
-        return sh.T == 64    ? batch_loop_launch<64, false, Oracle>(s, sh, lds, R, S, A, calc)
-               : sh.T == 128 ? batch_loop_launch<128, false, Oracle>(s, sh, lds, R, S, A, calc)
-                             : batch_loop_launch<256, false, Oracle>(s, sh, lds, R, S, A, calc);
+            return sh.T == 128 ? batch_loop_launch<128, true, Oracle, DRIVER>(s, sh, lds, R, S, A, calc)
+                               : batch_loop_launch<256, true, Oracle, DRIVER>(s, sh, lds, R, S, A, calc);
+        return sh.T == 64    ? batch_loop_launch<64, false, Oracle, DRIVER>(s, sh, lds, R, S, A, calc)
+               : sh.T == 128 ? batch_loop_launch<128, false, Oracle, DRIVER>(s, sh, lds, R, S, A, calc)
+                             : batch_loop_launch<256, false, Oracle, DRIVER>(s, sh, lds, R, S, A, calc);
     });
 }
 

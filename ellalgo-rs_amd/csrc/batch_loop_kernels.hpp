@@ -3,7 +3,8 @@
 // A workgroup owns the ellipsoids the batch engine gives it (batch_kernels.hpp: thread (e, i) = row i of local
 // ellipsoid e, Q in LDS) and, for each of them, runs up to `iters` rounds of
 //     oracle -> x_best -> scalar stage + rank-1 (batch_space_cut_apply, the code k_batch_update runs) -> stop test
-// without leaving the kernel: cutting_plane_optim (src/cutting_plane.rs:286-313) and cutting_plane_feas (:205-227), once.
+// without leaving the kernel: cutting_plane_optim (src/cutting_plane.rs:286-313) and cutting_plane_feas (:205-227), once, and
+// under DRIVER = BATCH_DRIVER_OPTIM_Q cutting_plane_optim_q (:331-374), whose rounds differ where marked Q below.
 // What differs between the problems is the Oracle policy (batch_lmi_kernels.hpp, batch_lowpass_kernels.hpp,
 // batch_svm_kernels.hpp): a type with
 //     struct Args                     what the oracle reads and keeps in HBM; a kernel argument, by value
@@ -13,7 +14,9 @@
 //     assess(A, R, live, i, n, xci, blk, r, g)    collective: x = xc, one oracle call, gradient into g; ends in a barrier
 //     outcome(A, feas, osc)           the answer found in an instance's scalars
 //     store(A, b, osc, r)             the oracle state back to HBM (thread 0 of the instance)
-// all static __device__ __forceinline__.  The skeleton never asks which oracle it serves.
+// all static __device__ __forceinline__.  The skeleton never asks which oracle it serves.  An oracle of the optim_q driver
+// (an OracleOptimQ) also names two of its scalars, Q_RETRY and Q_MORE_ALT: its assess reads `retry` from the first, leaves
+// `more_alt` in the second and the point x_q in the first n doubles of its block; load and store carry Q_RETRY through HBM.
 //
 // Barriers are workgroup-wide; stopped instances are masked off and the loop is driven by __syncthreads_or votes.  Every
 // loop is bounded by iters and the oracle's own bounds; no thread waits on another workgroup.
@@ -65,13 +68,20 @@ struct BatchOutcome {
     double b1;
 };
 
+// which of the reference's drivers a loop kernel runs
+enum : int {
+    BATCH_DRIVER_OPTIM = 0,    // cutting_plane_optim and, with R.feas, cutting_plane_feas
+    BATCH_DRIVER_OPTIM_Q = 1,  // cutting_plane_optim_q: discrete cuts (CUT_Q) and the retry after NoEffect
+};
+
 // STABLE: the spaces are EllStable buffers and a cut is batch_stable_cut_apply (batch_stable_apply.hpp).
-template <int T, bool STABLE, class Oracle>
+template <int T, bool STABLE, class Oracle, int DRIVER = BATCH_DRIVER_OPTIM>
 __global__ __launch_bounds__(T) void k_batch_loop(BatchParams P, BatchLoopRun R, double* __restrict__ Q,
                                                   double* __restrict__ xc, double* __restrict__ kappa,
                                                   double* __restrict__ tsq, BatchLoopState S, typename Oracle::Args A,
                                                   EllCalcDev calc) {
     extern __shared__ double sm[];
+    constexpr bool DRIVER_Q = DRIVER == BATCH_DRIVER_OPTIM_Q;
     const int n = P.n, pitch = P.pitch;
     const int tid = threadIdx.x;
     const int e = tid / n, i = tid - e * n;
@@ -124,11 +134,16 @@ __global__ __launch_bounds__(T) void k_batch_loop(BatchParams P, BatchLoopRun R,
         const BatchOutcome mine = Oracle::outcome(A, R.feas, osc);
         const bool found = live && mine.what == BOUT_FEAS;  // cutting_plane_feas: a feasible point ends the loop  :217-220
         const bool best = live && (mine.what == BOUT_SHRUNK || mine.what == BOUT_FEAS);
-        if (best) xb = xci;  // x_best = Some(space.xc())                                                           :303
+        if constexpr (DRIVER_Q) {
+            if (best) xb = blk[i];  // Q: x_best = Some(x_q), the oracle's point                                    :349
+        } else {
+            if (best) xb = xci;  // x_best = Some(space.xc())                                                       :303
+        }
         const bool upd = live && (mine.what == BOUT_CUT || mine.what == BOUT_SHRUNK);
         const BatchOutcome its = Oracle::outcome(A, R.feas, osc_s);
         const bool lane = lane_ok && osc_s[BL_STOPPED] == 0.0 && (its.what == BOUT_CUT || its.what == BOUT_SHRUNK);
-        const int kind = its.what == BOUT_SHRUNK ? CUT_CENTRAL : CUT_BIAS;  //                                      :301-307
+        // Q: update_q on every path                                                                       :301-307 / :352
+        const int kind = DRIVER_Q ? CUT_Q : its.what == BOUT_SHRUNK ? CUT_CENTRAL : CUT_BIAS;
         const double b0 = lane ? its.b0 : 0.0;
         const double b1 = lane ? its.b1 : 0.0;
         const int hb1 = lane ? its.has_b1 : 0;
@@ -142,6 +157,23 @@ __global__ __launch_bounds__(T) void k_batch_loop(BatchParams P, BatchLoopRun R,
             } else if (!upd) {  // the oracle found nothing to cut with
                 osc[BL_STATUS] = (double)ST_UNKNOWN;
                 stop = true;
+            } else if constexpr (DRIVER_Q) {  //                                                                    :347-371
+                const double st = sc[3];
+                if (best || st == (double)ST_SUCCESS) osc[Oracle::Q_RETRY] = 0.0;
+                if (st == (double)ST_NOSOLN || (st == (double)ST_NOEFFECT && osc[Oracle::Q_MORE_ALT] == 0.0)) {
+                    osc[BL_STATUS] = st;
+                    stop = true;
+                } else {
+                    if (st == (double)ST_NOEFFECT) osc[Oracle::Q_RETRY] = 1.0;  // the space is as it was; tsq was written
+                    osc[BL_STATUS] = (double)ST_SUCCESS;
+                    if (sc[5] < R.tol) {
+                        stop = true;
+                    } else {
+                        const double done = osc[BL_NITER] + 1.0;
+                        osc[BL_NITER] = done;
+                        stop = done >= (double)R.max_iters;
+                    }
+                }
             } else if (sc[3] != (double)ST_SUCCESS || sc[5] < R.tol) {  //                                          :308 / :222
                 osc[BL_STATUS] = sc[3];
                 stop = true;
