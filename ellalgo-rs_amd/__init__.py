@@ -7,6 +7,7 @@ sources (csrc/), the build recipe, the C++ host mirror of the reference's traits
 from . import build, capi, synth  # noqa: F401
 from .ell import (CutStatus, Ell, EllStable, ParallelCut, SingleCut, calc)  # noqa: F401
 from .batch import EllBatch, EllBatchStreamed, EllStableBatch, EllStableBatchStreamed  # noqa: F401
+from .batch_bsearch import BatchLinFeasProblem  # noqa: F401
 from .batch_lmi import BatchLmiProblem  # noqa: F401
 from .batch_lowpass import BatchLowpassProblem  # noqa: F401
 from .batch_maxcut import BatchMaxcutProblem  # noqa: F401
@@ -19,5 +20,5 @@ from .sharded_abi import ShardedEllAbi  # noqa: F401
 from .svm import SvmOracle  # noqa: F401
 
 __all__ = ["build", "capi", "synth", "CutStatus", "Ell", "EllStable", "ParallelCut", "SingleCut", "calc",
-           "EllBatch", "EllBatchStreamed", "EllStableBatch", "EllStableBatchStreamed", "BatchLmiProblem", "BatchLowpassProblem", "BatchMaxcutProblem", "BatchProfitProblem", "BatchSvmProblem", "LDLTMgr", "LMIOracle", "LMI0Oracle", "LmiLoopProblem", "LowpassOracle", "create_lowpass_case", "lowpass_case_constants",
+           "EllBatch", "EllBatchStreamed", "EllStableBatch", "EllStableBatchStreamed", "BatchLinFeasProblem", "BatchLmiProblem", "BatchLowpassProblem", "BatchMaxcutProblem", "BatchProfitProblem", "BatchSvmProblem", "LDLTMgr", "LMIOracle", "LMI0Oracle", "LmiLoopProblem", "LowpassOracle", "create_lowpass_case", "lowpass_case_constants",
            "SvmOracle"]
