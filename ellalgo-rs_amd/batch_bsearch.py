@@ -1,7 +1,9 @@
 """Python mirror of the batched linear feasibility oracles with a movable target and of the batched device-resident bsearch
 over them (include/ellhip_batch_bsearch.h): B `MyOracle3`-like oracles (src/example3.rs) of J rows in n variables, each
 with its own ellipsoid in an `EllBatch` or an `EllStableBatch`; `bsearch` runs the reference's `bsearch` over
-`BSearchAdaptor` (src/cutting_plane.rs:403-419, :441-466) for all of them in one kernel per chunk of rounds."""
+`BSearchAdaptor` (src/cutting_plane.rs:403-419, :441-466) for all of them in one kernel per chunk of rounds.
+`BatchLinFeasProblem.streamed` (include/ellhip_batch_bsearch_streamed.h) takes n up to 1024 and J up to 4096 and runs on an
+`EllBatchStreamed` or an `EllStableBatchStreamed`."""
 from __future__ import annotations
 
 import ctypes as C
@@ -28,22 +30,32 @@ PROTOTYPES = {
     "ellhip_batch_linfeas_bsearch_stable": _BSEARCH,
 }
 BATCH_BSEARCH_NAMES = sorted(PROTOTYPES)
+# every symbol include/ellhip_batch_bsearch_streamed.h declares (each as its counterpart above)
+STREAMED_PROTOTYPES = {
+    "ellhip_batch_linfeas_create_streamed": PROTOTYPES["ellhip_batch_linfeas_create"],
+    "ellhip_batch_linfeas_feas_streamed": _FEAS,
+    "ellhip_batch_linfeas_feas_streamed_stable": _FEAS,
+    "ellhip_batch_linfeas_bsearch_streamed": _BSEARCH,
+    "ellhip_batch_linfeas_bsearch_streamed_stable": _BSEARCH,
+}
+BATCH_BSEARCH_STREAMED_NAMES = sorted(STREAMED_PROTOTYPES)
 
 
 def _load():
     lib = capi.load()
     if getattr(lib.ellhip_batch_linfeas_create, "argtypes", None) is None:
-        for name, (res, args) in PROTOTYPES.items():
+        for name, (res, args) in {**PROTOTYPES, **STREAMED_PROTOTYPES}.items():
             fn = getattr(lib, name)  # a missing symbol is an error
             fn.restype, fn.argtypes = res, args
     return lib
 
 
 class BatchLinFeasProblem:
-    def __init__(self, a, c, B: int | None = None, *, device: int = -1):
+    def __init__(self, a, c, B: int | None = None, *, device: int = -1, _create: str = "ellhip_batch_linfeas_create"):
         """a [J][n] and c [J] with B: one table for all B problems; a [B][J][n] and c [B][J]: a table per problem.  The last
         entry of every c is never read (the last row's offset is the target)."""
         self._lib = _load()
+        self._by_handle = _create != "ellhip_batch_linfeas_create"  # made by `streamed`: the batch handle picks the engine
         a = np.ascontiguousarray(a, dtype=np.float64)
         c = np.ascontiguousarray(c, dtype=np.float64)
         if a.ndim == 2:
@@ -62,10 +74,16 @@ class BatchLinFeasProblem:
         else:
             raise ValueError("a must be [J][n] or [B][J][n]")
         h = C.c_void_p()
-        capi.check(self._lib.ellhip_batch_linfeas_create(C.byref(h), int(B), n, J, _p(a), _p(c), shared, int(device)),
-                   "ellhip_batch_linfeas_create")
+        capi.check(getattr(self._lib, _create)(C.byref(h), int(B), n, J, _p(a), _p(c), shared, int(device)), _create)
         self._h = h
         self.B, self.n, self.J = int(B), int(n), int(J)
+
+    @classmethod
+    def streamed(cls, a, c, B: int | None = None, *, device: int = -1):
+        """The same problems for 1 <= n <= 1024 and 1 <= J <= 4096 (include/ellhip_batch_bsearch_streamed.h): `feas` and
+        `bsearch` then run on the engine of the batch handle they are given, an `EllBatchStreamed` or an
+        `EllStableBatchStreamed` of dimension n among them."""
+        return cls(a, c, B, device=device, _create="ellhip_batch_linfeas_create_streamed")
 
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None
@@ -101,14 +119,15 @@ class BatchLinFeasProblem:
                    "ellhip_batch_linfeas_assess_feas")
         return grad, beta, cut
 
-    @staticmethod
-    def _entry(batch, name):
-        # (a streamed handle goes to the same entry points, which refuse it: the streamed form is not built)
+    def _entry(self, batch, name):
+        if self._by_handle:
+            return capi.batch_loop_entry(batch, name)
+        # (the plain constructor's dispatch: a streamed handle goes to the LDS entry points, which refuse it)
         return name + ("_stable" if batch.variant == capi.SPACE_ELL_STABLE else "")
 
     def feas(self, batch, max_iters: int, tol: float):
-        """cutting_plane_feas per problem on `batch` (an EllBatch or an EllStableBatch).  Returns (x [B][n] with NaN rows
-        where none is feasible, feasible [B], niter [B], status [B])."""
+        """cutting_plane_feas per problem on `batch` (an EllBatch or an EllStableBatch; a streamed one for `streamed`).
+        Returns (x [B][n] with NaN rows where none is feasible, feasible [B], niter [B], status [B])."""
         entry = self._entry(batch, "ellhip_batch_linfeas_feas")
         return capi.run_batch_loop(self._lib, entry, batch, self, None, max_iters, tol)
 

@@ -1,13 +1,16 @@
 // batch_linfeas_capi.inc.hpp -- C ABI of the batched linear feasibility oracles with a movable target and of the
 // device-resident bsearch over them (include/ellhip_batch_bsearch.h).  Included from ellhip_capi.hip after
 // batch_loop_capi.inc.hpp: the _feas entry points go through its driver, batch_loop_run; the bsearch entry points launch
-// k_batch_bsearch, which has a host loop of its own because its stop state is the bisection's, not the loop's.
+// k_batch_bsearch, which has a host loop of its own because its stop state is the bisection's, not the loop's.  That host
+// loop (batch_bsearch_drive), the argument checks and the constructor are shared with the streamed entry points of
+// batch_linfeas_streamed_capi.inc.hpp.
 //
 // Reference: src/example3.rs (oracle), src/cutting_plane.rs:205-227 (cutting_plane_feas), :403-419 (BSearchAdaptor),
 // :441-466 (bsearch).
 #include "../../include/ellhip_batch_bsearch.h"
 
 #include "batch_linfeas_kernels.hpp"
+#include "batch_linfeas_streamed_kernels.hpp"
 
 struct ellhip_batch_linfeas {
     BatchLoopBuffers loop;       // device, B, n, stream, the loop state of the _feas entry points
@@ -23,7 +26,7 @@ struct ellhip_batch_linfeas {
     double* d_beta = nullptr;    // assess: [B]
     int* d_cut = nullptr;        // assess: [B]
     // bsearch, allocated by the first call
-    double* d_bs = nullptr;      // [B][BS_N] the bisection state
+    double* d_bs = nullptr;      // [B][BSS_N] the bisection state (the LDS engines use [B][BS_N] of it)
     int* d_bs_nstopped = nullptr;
     double* d_pQ = nullptr;      // the probe's space: [B][n][n], [B][n], [B], [B]
     double* d_pxc = nullptr;
@@ -77,7 +80,7 @@ hipError_t batch_bsearch_alloc(ellhip_batch_linfeas* o) {
     if (o->d_bs) return hipSuccess;
     const size_t B = (size_t)o->B, n = (size_t)o->n;
     double* bs = nullptr;
-    hipError_t e = o->loop.mem.device(bs, B * BS_N * sizeof(double));
+    hipError_t e = o->loop.mem.device(bs, B * BSS_N * sizeof(double));
     if (e == hipSuccess) e = o->loop.mem.device(o->d_bs_nstopped, sizeof(int));
     if (e == hipSuccess) e = o->loop.mem.device(o->d_pQ, B * n * n * sizeof(double));
     if (e == hipSuccess) e = o->loop.mem.device(o->d_pxc, B * n * sizeof(double));
@@ -92,30 +95,36 @@ hipError_t batch_bsearch_alloc(ellhip_batch_linfeas* o) {
     return e;
 }
 
-int batch_linfeas_bsearch(ellhip_batch* s, ellhip_batch_linfeas* o, const double* lower, const double* upper,
-                          int64_t inner_max_iters, double inner_tol, int64_t max_iters, double tol, int32_t* feasible_out,
-                          int64_t* niter_out, double* upper_out, int64_t* rounds_out, int64_t* ends_out,
-                          BatchLoopEngine engine) {
+// What every bsearch entry point checks before anything is touched: the handle's kind against the entry point's engine,
+// B, n and the device, the iteration counts and the interval.
+int batch_bsearch_check(const ellhip_batch* s, const ellhip_batch_linfeas* o, const double* lower, const double* upper,
+                        int64_t inner_max_iters, int64_t max_iters, const int32_t* feasible_out, const int64_t* niter_out,
+                        const double* upper_out, const int64_t* rounds_out, BatchLoopEngine engine, const std::string& what) {
     if (!s || !o || !lower || !upper || !feasible_out || !niter_out || !upper_out || !rounds_out)
         return fail(ELLHIP_E_INVALID, "NULL argument");
-    const std::string what = "batched bsearch";
-    if (s->streamed)
-        return fail(ELLHIP_E_INVALID, (what + ": streamed batch handles are not supported: the streamed form is not built").c_str());
+    if (!engine.streamed && s->streamed)
+        return fail(ELLHIP_E_INVALID, (what + ": streamed batch handles are not supported: the LDS engines' kernel is not built "
+                                              "for streamed handles; use ellhip_batch_linfeas_bsearch_streamed").c_str());
     if (const int rc = batch_loop_check(s, engine, what)) return rc;
     if (s->B != o->B || s->n != o->n) return fail(ELLHIP_E_INVALID, (what + ": spaces and oracle differ in B or n").c_str());
     if (s->device != o->loop.device)
         return fail(ELLHIP_E_INVALID, (what + ": spaces and oracle live on different devices").c_str());
     if (max_iters < 0 || inner_max_iters < 0) return fail(ELLHIP_E_INVALID, "max_iters and inner_max_iters must be >= 0");
-    const size_t B = (size_t)o->B;
-    for (size_t b = 0; b < B; ++b)
+    for (long long b = 0; b < o->B; ++b)
         if (!(lower[b] <= upper[b]))  // the reference asserts                                     src/cutting_plane.rs:448
             return fail(ELLHIP_E_INVALID, (what + ": lower > upper").c_str());
-    const BatchLinFeasOracle::Args A = batch_linfeas_args(o);
-    const BatchLoopShape sh = batch_loop_shape(s, engine.stable);
-    const size_t lds =
-        (size_t)sh.epw * (sh.space_doubles + BatchLinFeasOracle::lds_doubles(A, s->n) + BS_N) * sizeof(double);
-    if (lds > BATCH_LOOP_LDS_MAX)
-        return fail(ELLHIP_E_INVALID, (what + ": this (n, J) needs more LDS than a workgroup has").c_str());
+    return 0;
+}
+
+// The host loop of every bsearch kernel.  The caller has checked its arguments (batch_bsearch_check, the LDS a launch
+// needs).  stride: the doubles of the kernel's state record, BS_N or BSS_N; launch(R, W) enqueues one launch of R.iters
+// rounds on s->stream and returns 0 or an error code.
+template <class Launch>
+int batch_bsearch_drive(ellhip_batch* s, ellhip_batch_linfeas* o, const double* lower, const double* upper,
+                        int64_t inner_max_iters, double inner_tol, int64_t max_iters, double tol, int32_t* feasible_out,
+                        int64_t* niter_out, double* upper_out, int64_t* rounds_out, int64_t* ends_out, int stride,
+                        Launch launch) {
+    const size_t B = (size_t)o->B, N = (size_t)stride;
     DeviceGuard guard(s->device);
     HIPCHK(hipStreamSynchronize(s->stream));
     HIPCHK(hipStreamSynchronize(o->loop.stream));
@@ -123,15 +132,15 @@ int batch_linfeas_bsearch(ellhip_batch* s, ellhip_batch_linfeas* o, const double
         const hipError_t e = batch_bsearch_alloc(o);
         if (e != hipSuccess) return fail(e == hipErrorOutOfMemory ? ELLHIP_E_NOMEM : ELLHIP_E_HIP, "batched bsearch allocation", e);
     }
-    std::vector<double> st(B * BS_N, 0.0);
+    std::vector<double> st(B * N, 0.0);
     for (size_t b = 0; b < B; ++b) {
-        double* v = st.data() + b * BS_N;
+        double* v = st.data() + b * N;
         v[BS_LOWER] = lower[b];
         v[BS_UPPER] = upper[b];
         v[BS_UORIG] = upper[b];  //                                                                                :449
         v[BS_INNER] = -1.0;      // between two probes
     }
-    HIPCHK(hipMemcpy(o->d_bs, st.data(), B * BS_N * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(o->d_bs, st.data(), B * N * sizeof(double), hipMemcpyHostToDevice));
     HIPCHK(fill_now(o->d_bs_nstopped, 0, sizeof(int), s->stream));
     BatchBsBuffers W;
     W.state = o->d_bs;
@@ -146,31 +155,22 @@ int batch_linfeas_bsearch(ellhip_batch* s, ellhip_batch_linfeas* o, const double
     R.inner_tol = inner_tol;
     R.max_iters = max_iters;
     R.tol = tol;
-    const EllCalcDev calc = EllCalcDev::make(s->n, s->use_parallel_cut);
     // A launch runs `chunk` rounds of every instance that has not stopped; an instance needs at most
     // max_iters * inner_max_iters of them, and one launch when no probe makes an oracle call.
     const long double need = (long double)max_iters * ((long double)inner_max_iters + 1.0L);
     const long double cap = std::ceil(need / (long double)o->loop.chunk);
     const long long launches = std::max<long long>(1, cap > 4.0e18L ? (long long)4000000000000000000LL : (long long)cap);
     for (long long l = 0; l < launches; ++l) {
-        int rc;
-        if (engine.stable)
-            rc = sh.T == 128 ? batch_bsearch_launch<128, true>(s, sh, lds, R, W, A, calc)
-                             : batch_bsearch_launch<256, true>(s, sh, lds, R, W, A, calc);
-        else
-            rc = sh.T == 64    ? batch_bsearch_launch<64, false>(s, sh, lds, R, W, A, calc)
-                 : sh.T == 128 ? batch_bsearch_launch<128, false>(s, sh, lds, R, W, A, calc)
-                               : batch_bsearch_launch<256, false>(s, sh, lds, R, W, A, calc);
-        if (rc) return rc;
+        if (const int rc = launch(R, W)) return rc;
         HIPCHK(hipGetLastError());
         int nstopped = 0;
         HIPCHK(hipMemcpyAsync(&nstopped, o->d_bs_nstopped, sizeof(int), hipMemcpyDeviceToHost, s->stream));
         HIPCHK(hipStreamSynchronize(s->stream));
         if ((long long)nstopped >= o->B) break;
     }
-    HIPCHK(hipMemcpy(st.data(), o->d_bs, B * BS_N * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(st.data(), o->d_bs, B * N * sizeof(double), hipMemcpyDeviceToHost));
     for (size_t b = 0; b < B; ++b) {
-        const double* v = st.data() + b * BS_N;
+        const double* v = st.data() + b * N;
         feasible_out[b] = v[BS_UPPER] != v[BS_UORIG];  //                                                     :454 / :465
         niter_out[b] = (int64_t)v[BS_NITER];
         upper_out[b] = v[BS_UPPER];
@@ -181,17 +181,40 @@ int batch_linfeas_bsearch(ellhip_batch* s, ellhip_batch_linfeas* o, const double
     return 0;
 }
 
-}  // namespace
+int batch_linfeas_bsearch(ellhip_batch* s, ellhip_batch_linfeas* o, const double* lower, const double* upper,
+                          int64_t inner_max_iters, double inner_tol, int64_t max_iters, double tol, int32_t* feasible_out,
+                          int64_t* niter_out, double* upper_out, int64_t* rounds_out, int64_t* ends_out,
+                          BatchLoopEngine engine) {
+    const std::string what = "batched bsearch";
+    if (const int rc = batch_bsearch_check(s, o, lower, upper, inner_max_iters, max_iters, feasible_out, niter_out, upper_out,
+                                           rounds_out, engine, what))
+        return rc;
+    const BatchLinFeasOracle::Args A = batch_linfeas_args(o);
+    const BatchLoopShape sh = batch_loop_shape(s, engine.stable);
+    const size_t lds =
+        (size_t)sh.epw * (sh.space_doubles + BatchLinFeasOracle::lds_doubles(A, s->n) + BS_N) * sizeof(double);
+    if (lds > BATCH_LOOP_LDS_MAX)
+        return fail(ELLHIP_E_INVALID, (what + ": this (n, J) needs more LDS than a workgroup has").c_str());
+    const EllCalcDev calc = EllCalcDev::make(s->n, s->use_parallel_cut);
+    return batch_bsearch_drive(s, o, lower, upper, inner_max_iters, inner_tol, max_iters, tol, feasible_out, niter_out,
+                               upper_out, rounds_out, ends_out, BS_N, [&](const BatchBsRun& R, const BatchBsBuffers& W) {
+        if (engine.stable)
+            return sh.T == 128 ? batch_bsearch_launch<128, true>(s, sh, lds, R, W, A, calc)
+                               : batch_bsearch_launch<256, true>(s, sh, lds, R, W, A, calc);
+        return sh.T == 64    ? batch_bsearch_launch<64, false>(s, sh, lds, R, W, A, calc)
+               : sh.T == 128 ? batch_bsearch_launch<128, false>(s, sh, lds, R, W, A, calc)
+                             : batch_bsearch_launch<256, false>(s, sh, lds, R, W, A, calc);
+    });
+}
 
-extern "C" {
-
-int ellhip_batch_linfeas_create(ellhip_batch_linfeas** out, int64_t B, int64_t n, int64_t J, const double* a,
-                                const double* c, int32_t shared, int device) {
+// ellhip_batch_linfeas_create and _create_streamed: the limits are the entry point's
+int batch_linfeas_create(ellhip_batch_linfeas** out, int64_t B, int64_t n, int64_t J, const double* a, const double* c,
+                         int32_t shared, int device, int nmax, int jmax) {
     if (!out) return fail(ELLHIP_E_INVALID, "out is NULL");
     *out = nullptr;
     if (B < 1 || B > (1 << 24)) return fail(ELLHIP_E_INVALID, "batched linfeas: need 1 <= B <= 2^24");
-    if (n < 1 || n > BATCH_NMAX) return fail(ELLHIP_E_INVALID, "batched linfeas: need 1 <= n <= 128");
-    if (J < 1 || J > BATCH_LINFEAS_JMAX) return fail(ELLHIP_E_INVALID, "batched linfeas: need 1 <= J <= 512");
+    if (n < 1 || n > nmax) return fail(ELLHIP_E_INVALID, ("batched linfeas: need 1 <= n <= " + std::to_string(nmax)).c_str());
+    if (J < 1 || J > jmax) return fail(ELLHIP_E_INVALID, ("batched linfeas: need 1 <= J <= " + std::to_string(jmax)).c_str());
     if (!a || !c) return fail(ELLHIP_E_INVALID, "NULL argument");
     const int ndev = ellhip_device_count();
     if (ndev <= 0) return fail(ELLHIP_E_NODEVICE, "no HIP device: the batched linfeas oracle has no CPU path");
@@ -231,6 +254,15 @@ int ellhip_batch_linfeas_create(ellhip_batch_linfeas** out, int64_t B, int64_t n
     return 0;
 }
 
+}  // namespace
+
+extern "C" {
+
+int ellhip_batch_linfeas_create(ellhip_batch_linfeas** out, int64_t B, int64_t n, int64_t J, const double* a,
+                                const double* c, int32_t shared, int device) {
+    return batch_linfeas_create(out, B, n, J, a, c, shared, device, BATCH_NMAX, BATCH_LINFEAS_JMAX);
+}
+
 void ellhip_batch_linfeas_destroy(ellhip_batch_linfeas* o) {
     if (!o) return;
     DeviceGuard guard(o->loop.device);
@@ -267,12 +299,16 @@ int ellhip_batch_linfeas_assess_feas(ellhip_batch_linfeas* o, const double* x, d
     const size_t B = (size_t)o->B, n = (size_t)o->n;
     const BatchLinFeasOracle::Args A = batch_linfeas_args(o);
     const size_t per = BatchLinFeasOracle::lds_doubles(A, o->n) + n;
-    const BatchRowShape sh = batch_row_shape(o->n, per);
+    const bool wide = o->n > BATCH_NMAX;  // past the LDS engines' block: one workgroup per problem, n rounded up to whole waves
+    const BatchRowShape sh = wide ? BatchRowShape{} : batch_row_shape(o->n, per);  // (epw = 1 when wide)
     const size_t lds = (size_t)sh.epw * per * sizeof(double);
     const unsigned grid = (unsigned)((o->B + sh.epw - 1) / sh.epw);
     HIPCHK(hipStreamSynchronize(o->loop.stream));
     HIPCHK(hipMemcpy(o->d_x, x, B * n * sizeof(double), hipMemcpyHostToDevice));
-    if (sh.T == 128)
+    if (wide)
+        hipLaunchKernelGGL(k_batch_linfeas_assess_wg, dim3(grid), dim3((unsigned)((o->n + 63) / 64 * 64)), lds, o->loop.stream,
+                           o->n, A, (const double*)o->d_x, o->d_grad, o->d_beta, o->d_cut);
+    else if (sh.T == 128)
         hipLaunchKernelGGL(k_batch_linfeas_assess<128>, dim3(grid), dim3(128), lds, o->loop.stream, o->B, o->n, sh.epw, A,
                            (const double*)o->d_x, o->d_grad, o->d_beta, o->d_cut);
     else

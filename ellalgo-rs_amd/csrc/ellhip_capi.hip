@@ -638,3 +638,4 @@ int ellhip_profile_read(ellhip_space* s, double* ms_out, int64_t* count_out) {
 #include "batch_maxcut_capi.inc.hpp"
 #include "batch_profit_capi.inc.hpp"
 #include "batch_linfeas_capi.inc.hpp"
+#include "batch_linfeas_streamed_capi.inc.hpp"
